@@ -20,7 +20,10 @@ touches any GPU) and relays rank 0's line.
 graph, started together (the latency-bound hidden stack of one fit overlaps the HBM-bound layer-1 kernels of the
 other); value counts the samples of all of them.  The headline configuration is R = 1.
 
-The JSON line also carries
+A plain run sets up, warms up, times the --steps epochs and prints the line; `roofline` and `cpu_baseline` are null in it.
+`final_loss` / `final_val_loss` are the history row of the last epoch run: the last timed one, or with --full the last of
+the roofline's two instrumented epochs.  --full adds the measurements below (each takes runs of its own after the timed
+epochs):
   roofline      the dominant kernel (l1_bwd_adam: fused layer-1 backward + Adam): algorithmic bytes per launch / its
                 mean duration from HIP events recorded on the launch stream immediately before and after that
                 kernel, vs 8 TB/s HBM.  `traffic` = PMC-measured bytes per launch from the committed rocprofv3
@@ -31,7 +34,10 @@ The JSON line also carries
                 bounded to ~12 s; `numpy_port` = the single-threaded-Adam NumPy oracle step for comparison.
   l1_gemm       (N=1) a dozen-number summary of the large-M first-layer genotype GEMM (model.predict) in the default
                 predict mode as a fraction of the dense bf16-MFMA peak (l1_gemm_summary).  The full mode x shape sweep
-                lives in tools/l1_gemm_sweep.py / --l1-gemm-full FILE and never enters the line.
+                lives in tools/l1_gemm_sweep.py / --full --l1-gemm-full FILE and never enters the line.
+
+--dump-outputs DIR writes what the timed fit hands its caller after its last timed epoch as DIR/<name>.npy (dump_outputs), so
+that two builds can be compared output for output: the inputs are seeded and identical from run to run.
 
 The line is the last thing printed, strict JSON, at most MAX_LINE_BYTES (format_line; tests/test_host.py).
 """
@@ -236,6 +242,38 @@ def cpu_baseline(x, y_norm, train, test, K, H, seconds):
     return out
 
 
+DUMP_SNPS = 4096             # --dump-outputs: SNPs in the seeded sample of the per-SNP parameters (W1 is 100 MB at the headline size)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(folder, fits, K):
+    """--dump-outputs DIR: for every fit of this process, after its last timed epoch, the arrays a caller of the fit receives -
+    the weights as they stand (`params_*`), the ModelCheckpoint copy (`best_*`), both in Keras orientation
+    (LocatorNet.export_params), and the history rows of every epoch run (`loss`, `val_loss`, `learning_rate`, float64).  The
+    per-SNP parameters (first-layer kernel rows W0, BN gamma / beta / moving mean / variance) are a fixed seeded sample of
+    DUMP_SNPS SNPs, listed in `snp_sample`; everything else is whole.  Parameters are float32, as the device holds them.  A
+    second fit's names start with `fit1_`, and so on."""
+    snps = np.sort(np.random.default_rng(0).choice(K, min(K, DUMP_SNPS), replace=False))
+    arrays = {"snp_sample": snps.astype(np.float64)}
+    for r, f in enumerate(fits):
+        pre = f"fit{r}_" if r else ""
+        for tag, flat in (("params", f.net.params), ("best", f.net.best)):
+            p = f.net._export_flat(flat)
+            for i, (w, b) in enumerate(zip(p["W"], p["b"])):
+                arrays[f"{pre}{tag}_W{i}"] = np.ascontiguousarray(w[snps] if i == 0 else w, dtype=np.float32)
+                arrays[f"{pre}{tag}_b{i}"] = np.ascontiguousarray(b, dtype=np.float32)
+            for k in ("gamma", "beta", "mov_mean", "mov_var"):
+                arrays[f"{pre}{tag}_{k}"] = np.ascontiguousarray(p[k][snps], dtype=np.float32)
+        for k, v in f.loop.hist.history.items():
+            arrays[f"{pre}{k}"] = np.asarray(v, dtype=np.float64)
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes > {DUMP_MAX_BYTES} (fewer --replicates-per-gpu)")
+    os.makedirs(folder, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(folder, k + ".npy"), v)
+
+
 def spawn_ranks(args):
     """--gpus N > 1 without a launcher: start the N rank processes (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in
     their environment) and relay rank 0's output.  Runs before this process has touched a GPU and never touches one."""
@@ -299,10 +337,14 @@ def main():
     ap.add_argument("--l1-bwd-grid", type=int, default=0,
                     help="workgroups of the layer-1 backward (measurement switch; default 2 x CUs; e.g. 2 x CUs - 32 leaves "
                          "some CUs with one backward workgroup so a second fit's stack waves can co-reside)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-l1-gemm", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed epochs also measure the roofline, the l1_gemm summary and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the fit's outputs after the last timed epoch to DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-l1-gemm", action="store_true", help="with --full: leave out the l1_gemm summary")
     ap.add_argument("--l1-gemm-full", default=None, metavar="FILE",
-                    help="also run the full predict-mode x shape GEMM sweep (tools/l1_gemm_sweep.py) and write it to FILE")
+                    help="with --full: also run the full predict-mode x shape GEMM sweep (tools/l1_gemm_sweep.py) and write it to FILE")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-graph", action="store_true", help="enqueue every kernel from the host each epoch")
     ap.add_argument("--side-stats", action="store_true",
@@ -322,6 +364,8 @@ def main():
     ap.add_argument("--selftest-launch", action="store_true",
                     help="testing (no GPU needed): only the rank launch + barrier + max-over-ranks plumbing, over gloo")
     args = ap.parse_args()
+    if args.l1_gemm_full and not args.full:
+        ap.error("--l1-gemm-full is part of --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
@@ -443,10 +487,12 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, fits, K)
 
-    # ---- dominant-kernel timing: HIP events around every l1_bwd_adam launch, recorded on the launch stream
+    # ---- dominant-kernel timing (--full): HIP events around every l1_bwd_adam launch, recorded on the launch stream
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         lib = _lib.load()
         import ctypes as C
         f0 = fits[0]
@@ -502,13 +548,14 @@ def main():
                        "chained_steps": bool(fits[0].runner.chain), "epochs_in_flight": 0 if args.sync_epochs else 2,
                        "replicates_per_gpu": R,
                        "replicates": ("single model" if world == 1 and R == 1 else
-                                      f"{R} model(s) per GPU, bootstrap resample per replicate")},
+                                      f"{R} model(s) per GPU, bootstrap resample per replicate"),
+                       "full": args.full},
             "us_per_minibatch_step": round(ms_epoch * 1e3 / steps_per_epoch / R, 2),
             "whole_step_hbm_frac": round(R * step_b / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
             "final_loss": round(fits[0].hist[-1][0], 5), "final_val_loss": round(fits[0].hist[-1][1], 5),
             "roofline": roof,
         }
-        if world == 1 and not args.no_l1_gemm:
+        if world == 1 and args.full and not args.no_l1_gemm:
             out["l1_gemm"] = l1_gemm_summary(fits[0].net, n)
             if args.l1_gemm_full:
                 # the full predict-mode x shape sweep goes to a FILE, never into the line (round 4's 24 KB line was unparseable)
@@ -517,7 +564,7 @@ def main():
                 full["tolerances"] = l1_gemm_sweep.PREDICT_MODE_INFO
                 with open(args.l1_gemm_full, "w") as f:
                     json.dump(full, f, indent=1)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(x, np.nan_to_num(ynorm), train, test, K, H, args.cpu_seconds)
         else:
             out["cpu_baseline"] = None

@@ -592,6 +592,57 @@ def test_bench_line_is_short_strict_json_with_the_contract_keys(repo_root):
         bench.format_line({k: v for k, v in out.items() if k != "roofline"})
 
 
+def test_bench_dump_outputs_are_float_npy_of_a_fixed_sample(repo_root, tmp_path, monkeypatch):
+    """bench.py --dump-outputs DIR (dump_outputs, on stand-in fits): the weights and the checkpoint copy in Keras orientation,
+    the per-SNP parameters at one fixed seeded sample of SNPs, the history in float64, every file float32 / float64, a second
+    fit under its own prefix, and a dump above the size cap refused before anything is written."""
+    import importlib.util
+    import subprocess
+    import types
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(repo_root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    K, H = 10_000, 8
+
+    def fake_fit(seed):
+        def export(flat):
+            rng = np.random.default_rng(seed + flat)
+            W = [rng.random((K, H)), rng.random((H, H)), rng.random((H, 2)), rng.random((2, 2))]
+            b = [rng.random(H), rng.random(H), rng.random(2), rng.random(2)]
+            return dict(W=W, b=b, **{k: rng.random(K) for k in ("gamma", "beta", "mov_mean", "mov_var")})
+        net = types.SimpleNamespace(params=0, best=1, _export_flat=export)
+        hist = {"loss": [1.0, 0.5], "val_loss": [1.1, 0.6], "learning_rate": [1e-3, 1e-3]}
+        return types.SimpleNamespace(net=net, loop=types.SimpleNamespace(hist=types.SimpleNamespace(history=hist)))
+
+    fits = [fake_fit(0), fake_fit(10)]
+    bench.dump_outputs(str(tmp_path / "a"), fits, K)
+    bench.dump_outputs(str(tmp_path / "b"), fits, K)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert all(f.endswith(".npy") for f in os.listdir(tmp_path / "a"))
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    snps = got["snp_sample"].astype(np.int64)
+    assert len(snps) == bench.DUMP_SNPS and np.all(np.diff(snps) > 0) and snps[-1] < K
+    for pre, fit in (("", fits[0]), ("fit1_", fits[1])):
+        for tag, flat in (("params", 0), ("best", 1)):
+            p = fit.net._export_flat(flat)
+            np.testing.assert_array_equal(got[f"{pre}{tag}_W0"], p["W"][0][snps].astype(np.float32))
+            np.testing.assert_array_equal(got[f"{pre}{tag}_W1"], p["W"][1].astype(np.float32))
+            np.testing.assert_array_equal(got[f"{pre}{tag}_b3"], p["b"][3].astype(np.float32))
+            np.testing.assert_array_equal(got[f"{pre}{tag}_mov_var"], p["mov_var"][snps].astype(np.float32))
+        assert got[f"{pre}val_loss"].dtype == np.float64 and list(got[f"{pre}val_loss"]) == [1.1, 0.6]
+    for name, v in got.items():                                          # same arguments, same files
+        np.testing.assert_array_equal(np.load(tmp_path / "b" / f"{name}.npy"), v)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1 << 16)
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / "c"), fits, K)
+    assert not (tmp_path / "c").exists()
+    # the full GEMM sweep belongs to --full
+    r = subprocess.run([sys.executable, os.path.join(repo_root, "bench.py"), "--l1-gemm-full", str(tmp_path / "s.json")],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--full" in r.stderr
+
+
 def test_jacknife_draws_reproduce_the_reference_loop_and_its_rng_stream():
     """locator.py:713-727 draws, per replicate, the redrawn sites and then one np.random.binomial(2, af[i], n_pred)
     PER SITE in a Python loop.  jacknife_draws issues one broadcast binomial per replicate: same values, and the

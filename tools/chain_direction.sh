@@ -10,7 +10,7 @@ ALT=${ALT:-build/liblocator_hip_chalt.so}
 for rep in 1 2 3; do
   for m in 0 -1 9 15; do
     for lib in "" "--lib $ALT"; do
-      python3 bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-l1-gemm --nt-mask $m $lib $EXTRA 2>/dev/null | python3 -c "
+      python3 bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-l1-gemm --nt-mask $m $lib $EXTRA 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); r=d['roofline']
 print(json.dumps({'rep':$rep,'nt_mask':$m,'lib':'$lib' or 'product','samples_per_s':round(d['value']),'ms_per_epoch':d['ms_per_step'],'chain_frac':r['frac'],'chain_TBps':r['achieved']}))"

@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out
 mkdir -p $O
 rm -rf $O/cp1 $O/cp2 $O/cp3 $O/cp4
-B="python3 $R/bench.py --steps 2 --warmup 2 --no-cpu-baseline --no-l1-gemm --no-graph --separate-tail"
+B="python3 $R/bench.py --full --steps 2 --warmup 2 --no-cpu-baseline --no-l1-gemm --no-graph --separate-tail"
 timeout 200 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES -d $O/cp1 -o p --output-format csv -- $B > $O/cp1.log 2>&1
 timeout 200 rocprofv3 --kernel-trace --pmc SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_WAIT_INST_LDS SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_SALU -d $O/cp2 -o p --output-format csv -- $B > $O/cp2.log 2>&1
 timeout 200 rocprofv3 --kernel-trace --pmc SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_INST_LEVEL_VMEM SQ_INST_LEVEL_LDS -d $O/cp3 -o p --output-format csv -- $B > $O/cp3.log 2>&1
@@ -30,7 +30,7 @@ for f in glob.glob("$O/cp4/**/*kernel_trace.csv", recursive=True):
         k = short(r["Kernel_Name"])
         if want(k):
             dur[k].append(float(r["End_Timestamp"]) - float(r["Start_Timestamp"]))
-out = {"source": "tools/chain_pmc.sh (bench.py --steps 2 --warmup 2 --no-graph --separate-tail; 1000 x 100,000 SNPs)"}
+out = {"source": "tools/chain_pmc.sh (bench.py --full --steps 2 --warmup 2 --no-graph --separate-tail; 1000 x 100,000 SNPs)"}
 for k, v in acc.items():
     m = {c: sum(x) / len(x) for c, x in v.items()}
     waves = 2048.0

@@ -1,5 +1,5 @@
 cd /root/repo
-run() { python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-l1-gemm "$@" 2>/dev/null | python -c "
+run() { python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-l1-gemm "$@" 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['us_per_launch'])"; }
 echo "default: $(run)"; echo "default: $(run)"

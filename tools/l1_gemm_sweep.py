@@ -2,14 +2,14 @@
 """The full large-M layer-1 GEMM sweep (every predict mode x every shape), moved out of bench.py's headline line in round 5.
 
     python tools/l1_gemm_sweep.py [--out profiles/rNN_l1_gemm_sweep.json] [--snps 100000] [--n 1000]
-    python bench.py --l1-gemm-full profiles/rNN_l1_gemm_sweep.json        (same sweep on the bench's own fitted net)
+    python bench.py --full --l1-gemm-full profiles/rNN_l1_gemm_sweep.json (same sweep on the bench's own fitted net)
 
 One record per shape x mode: the large-M first-layer genotype GEMM (model.predict over all 1000 rows; 4096 / 16384 rows of
 the same matrix = the batched --jacknife; 4096 / 16384 DISTINCT rows streaming from HBM) as a fraction of the dense
 bf16-MFMA peak, for every predict mode the CLI ships - int8 x 3 digit planes (exact), int8 x 2 (the default while the
 dynamic-range guard allows it), bf16 x 3 / 2 / 1 pieces - plus the in-loop-conversion kernel used for few rows.  The
 tolerance each mode's PREDICTIONS are tested to is written once, in PREDICT_MODE_INFO below and DESIGN.md §5.
-bench.py's line carries only the dozen-number summary of the default mode (bench.py: l1_gemm_summary).
+bench.py --full carries in its line only the dozen-number summary of the default mode (bench.py: l1_gemm_summary).
 """
 import argparse
 import json

@@ -62,7 +62,7 @@ def main():
     cal_name = next((k for k in out if k.startswith("snapshot_if_kernel")), "__amd_rocclr_copyBuffer")
     cal = out.get(cal_name)
     doc = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) --kernel-trace -- python3 "
-                     "bench.py --steps 2 --warmup 2 --no-cpu-baseline --no-l1-gemm --no-graph; tools/pmc_traffic.sh",
+                     "bench.py --full --steps 2 --warmup 2 --no-cpu-baseline --no-l1-gemm --no-graph; tools/pmc_traffic.sh",
            "workload": {"K": K, "H": H, "n": n},
            "kernel_sources_sha256_16": kernel_sources_sha(),
            "units": "FETCH_SIZE/WRITE_SIZE in KiB; FETCH_SIZE doubled for wide (16 B/lane) streaming reads per "

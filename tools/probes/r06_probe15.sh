@@ -8,7 +8,7 @@ runpy.run_path("bench.py", run_name="__main__")
 PY
 for rep in 1 2 3; do for mode in plain early; do
 if [ $mode = plain ]; then CMD="python3 bench.py"; elif [ $mode = early ]; then CMD="env PYTHONPATH=$GRAFT_REPO_ROOT python3 /tmp/early.py"; else CMD="python3 bench.py --lib locator_amd/liblocator_hip.so"; fi
-$CMD --steps ${STEPS:-30} --warmup 5 --no-cpu-baseline --no-l1-gemm 2>/dev/null | python3 -c "
+$CMD --full --steps ${STEPS:-30} --warmup 5 --no-cpu-baseline --no-l1-gemm 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); r=d['roofline']
 print('$mode', round(d['value']), d['ms_per_step'], 'step_us', d['us_per_minibatch_step'], r.get('us_per_launch'))"

@@ -1,13 +1,13 @@
 #!/bin/bash
 # Regenerates the round's profile evidence on the GPU box (repo root):  bash tools/profile_round.sh r02
-#   gpurun_out/<tag>_bench_default.json          python3 bench.py --steps 20 --warmup 5          (the driver's command)
-#   gpurun_out/<tag>_bench_kernel_stats.csv      rocprofv3 --kernel-trace --stats of the same command
-#   gpurun_out/<tag>_bench_profiled.json         the bench line printed under the profiler
-#   gpurun_out/<tag>_bench_replicates2.json      python3 bench.py --replicates-per-gpu 2
-#   gpurun_out/<tag>_bench_2ranks_selflaunch.json  python3 bench.py --gpus 2 --device-index 0 --dist-backend gloo (no launcher)
-#   gpurun_out/<tag>_pmc_traffic.json            FETCH_SIZE / WRITE_SIZE passes (tools/pmc_traffic.sh)
-#   gpurun_out/<tag>_chain_pmc.json              SQ counters of the chained layer-1 kernel (tools/chain_pmc.sh)
-#   gpurun_out/<tag>_gemm_pmc_1000.json, _4096.json, <tag>_gemm_kernel_stats.csv   large-M GEMM counters (with the effective
+#   $O/<tag>_bench_default.json          python3 bench.py --full --steps 20 --warmup 5   (the headline run with every extra)
+#   $O/<tag>_bench_kernel_stats.csv      rocprofv3 --kernel-trace --stats of the same command
+#   $O/<tag>_bench_profiled.json         the bench line printed under the profiler
+#   $O/<tag>_bench_replicates2.json      python3 bench.py --full --replicates-per-gpu 2
+#   $O/<tag>_bench_2ranks_selflaunch.json  python3 bench.py --full --gpus 2 --device-index 0 --dist-backend gloo (no launcher)
+#   $O/<tag>_pmc_traffic.json            FETCH_SIZE / WRITE_SIZE passes (tools/pmc_traffic.sh)
+#   $O/<tag>_chain_pmc.json              SQ counters of the chained layer-1 kernel (tools/chain_pmc.sh)
+#   $O/<tag>_gemm_pmc_1000.json, _4096.json, <tag>_gemm_kernel_stats.csv   large-M GEMM counters (with the effective
 #                                                 clock from GRBM_GUI_ACTIVE) and kernel times, int8 and bf16 kernels
 # Copy what should be judged into profiles/ (tracked).
 TAG=${1:-r06}
@@ -20,12 +20,12 @@ bash $R/tools/pmc_traffic.sh > $O/pmc_traffic.log 2>&1
 cp $O/pmc_traffic.json $O/${TAG}_pmc_traffic.json
 cp $O/pmc_traffic.json $R/profiles/${TAG}_pmc_traffic.json
 cd $R
-python3 bench.py --steps 20 --warmup 5 > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
-python3 bench.py --steps 50 --warmup 5 --replicates-per-gpu 2 --no-cpu-baseline --no-l1-gemm > $O/${TAG}_bench_replicates2.json 2>> $O/${TAG}_bench_default.err
-python3 bench.py --gpus 2 --device-index 0 --dist-backend gloo --steps 20 --warmup 5 > $O/${TAG}_bench_2ranks_selflaunch.json 2>> $O/${TAG}_bench_default.err
+python3 bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
+python3 bench.py --full --steps 50 --warmup 5 --replicates-per-gpu 2 --no-cpu-baseline --no-l1-gemm > $O/${TAG}_bench_replicates2.json 2>> $O/${TAG}_bench_default.err
+python3 bench.py --full --gpus 2 --device-index 0 --dist-backend gloo --steps 20 --warmup 5 > $O/${TAG}_bench_2ranks_selflaunch.json 2>> $O/${TAG}_bench_default.err
 cd /tmp
 rm -rf $O/prof_kt; mkdir -p $O
-rocprofv3 --kernel-trace --stats -d $O/prof_kt -o k --output-format csv -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/${TAG}_bench_profiled.json 2> $O/prof_kt.err
+rocprofv3 --kernel-trace --stats -d $O/prof_kt -o k --output-format csv -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/${TAG}_bench_profiled.json 2> $O/prof_kt.err
 cp $O/prof_kt/k_kernel_stats.csv $O/${TAG}_bench_kernel_stats.csv
 bash $R/tools/chain_pmc.sh > $O/chain_pmc.log 2>&1               # counters of the chained layer-1 kernel alone
 cp $O/chain_pmc.json $O/${TAG}_chain_pmc.json
@@ -50,10 +50,10 @@ python3 tools/quant_study.py --out $O/${TAG}_quant_study.jsonl > $O/quant_study.
 bash tools/config1_timeline.sh ${TAG} > $O/config1_timeline.log 2>&1
 bash tools/config1_timeline.sh ${TAG}sync --sync >> $O/config1_timeline.log 2>&1
 python3 tools/predict_timeline.py --mode auto > $O/${TAG}_predict_timeline.jsonl 2>/dev/null
-for w in 512 128 64; do python3 bench.py --steps 20 --warmup 4 --width $w --no-cpu-baseline --no-l1-gemm > $O/${TAG}_bench_width$w.json 2>/dev/null; python3 bench.py --steps 20 --warmup 4 --width $w --no-chain --no-cpu-baseline --no-l1-gemm > $O/${TAG}_bench_width${w}_unchained.json 2>/dev/null; done
-for b in 64 128; do python3 bench.py --steps 20 --warmup 4 --batch $b --no-cpu-baseline --no-l1-gemm > $O/${TAG}_bench_batch$b.json 2>/dev/null; done
-python3 bench.py --steps 20 --warmup 4 --batch 64 --no-chain --no-cpu-baseline --no-l1-gemm > $O/${TAG}_bench_batch64_unchained.json 2>/dev/null
-python3 bench.py --steps 40 --warmup 5 --sync-epochs --no-cpu-baseline --no-l1-gemm > $O/${TAG}_bench_sync_epochs.json 2>/dev/null
+for w in 512 128 64; do python3 bench.py --full --steps 20 --warmup 4 --width $w --no-cpu-baseline --no-l1-gemm > $O/${TAG}_bench_width$w.json 2>/dev/null; python3 bench.py --full --steps 20 --warmup 4 --width $w --no-chain --no-cpu-baseline --no-l1-gemm > $O/${TAG}_bench_width${w}_unchained.json 2>/dev/null; done
+for b in 64 128; do python3 bench.py --full --steps 20 --warmup 4 --batch $b --no-cpu-baseline --no-l1-gemm > $O/${TAG}_bench_batch$b.json 2>/dev/null; done
+python3 bench.py --full --steps 20 --warmup 4 --batch 64 --no-chain --no-cpu-baseline --no-l1-gemm > $O/${TAG}_bench_batch64_unchained.json 2>/dev/null
+python3 bench.py --full --steps 40 --warmup 5 --sync-epochs --no-cpu-baseline --no-l1-gemm > $O/${TAG}_bench_sync_epochs.json 2>/dev/null
 tail -c 1500 $O/${TAG}_bench_default.json; echo; cat $O/${TAG}_bench_replicates2.json | cut -c1-200; echo; cat $O/${TAG}_bench_2ranks_selflaunch.json | cut -c1-300; echo
 head -12 $O/${TAG}_bench_kernel_stats.csv | cut -c1-150
 tail -6 $O/pmc_traffic.log; tail -4 $O/gemm_pmc.log | cut -c1-400
