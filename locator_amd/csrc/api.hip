@@ -134,7 +134,7 @@ extern "C" int loc_train_chain_supported(const loc_net* net) {
     return d->L >= 2 && net->wht && loc_stack_fused_supported(d->Hp) && loc_l1_chain_supported(d->Hp) &&
            (net->slot_rows <= LOC_ROWS || (net->slot_rows <= LOC_CHAIN_MAX_ROWS && d->Hp == 256)) && !in_drop &&
            (int64_t)chain_groups_of(net) * 32 * chain_rb_of(net) * d->Hp <= partial_floats_of(d) &&
-           (int64_t)d->Kp * 1024 < ((int64_t)1 << 32) && (net->x_pitch % 16) == 0;
+           l1_chain_offsets_fit(d) && (net->x_pitch % 16) == 0;
 }
 
 static int train_step_impl(const loc_net* net, const int32_t* rows, int n_b, int t_off, const uint8_t* mask,

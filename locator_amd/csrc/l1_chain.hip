@@ -210,7 +210,8 @@ __global__ __launch_bounds__(512) void l1_bwd_adam_chain_kernel(
     const float alpha = adam_alpha(alpha_tab, alpha_tab_len, lr, t_base, t_off);
     const bool chain = rows_next != nullptr;
 
-    // byte offset of this lane's first 16 bytes of unit (kt, w) in each of W1S / m / v  (Kp * 1024 < 2^32: checked by the launcher)
+    // byte offset of this lane's first 16 bytes of unit (kt, w) in each of W1S / m / v  (Kp * max(Hp, 256) * 4 < 2^32: checked
+    // by the launcher, l1_chain_offsets_fit)
     auto unit_off = [&](int kt, int ut) { return (uint32_t)(((uint32_t)kt * NHT + ut) * 4096u + lane * 16u); };
     auto load_unit = [&](int kt, int ut, f32x4 (&wq)[4], f32x4 (&mq)[4], f32x4 (&vq)[4]) {
         // 12 loads, ALWAYS (the wait counts depend on it).  kt < 0: nothing left to fetch -- the same 12 instructions with
@@ -562,6 +563,10 @@ __global__ __launch_bounds__(512) void l1_bwd_adam_chain_kernel(
 }
 
 extern "C" int loc_l1_chain_supported(int Hp) { return Hp == 512 || Hp == 256 || Hp == 128 || Hp == 64; }
+// Largest Kp whose W1 / m / v byte offsets fit the kernel's 32-bit lane offsets (unit_off reaches Kp * Hp * 4 bytes at the
+// end of the last k-tile): 2,097,120 at width 512.  Widths 64 and 128 keep the width-256 limit, 4,194,272
+int64_t l1_chain_max_kp(int Hp) { return ((((int64_t)1 << 32) - 1) / (4 * (int64_t)(Hp > 256 ? Hp : 256))) / 32 * 32; }
+bool l1_chain_offsets_fit(const loc_dims* d) { return (int64_t)d->Kp <= l1_chain_max_kp(d->Hp); }
 // partial groups the chained kernel leaves per workgroup (k-tile slots a workgroup owns at a time)
 extern "C" int loc_l1_chain_groups_per_workgroup(int Hp) { return loc_l1_chain_supported(Hp) ? ch_ktw(Hp / 32) : 0; }
 
@@ -596,8 +601,9 @@ int l1_chain_launch(const uint8_t* X, int64_t x_pitch, const int32_t* rows, int 
                       "(loc_param_layout)");
         return -1;
     }
-    if ((int64_t)d->Kp * 1024 >= ((int64_t)1 << 32)) {
-        loc_set_error("loc_l1_backward_adam_chain: more than 4M SNPs exceed the kernel's 32-bit byte offsets");
+    if (!l1_chain_offsets_fit(d)) {
+        loc_set_error("loc_l1_backward_adam_chain: %d SNPs (padded %d) at width %d exceed the kernel's 32-bit byte offsets "
+                      "(at most %lld padded SNPs at this width)", d->K, d->Kp, d->Hp, (long long)l1_chain_max_kp(d->Hp));
         return -1;
     }
     const int nht = d->Hp / 32, ktw = ch_ktw(nht);

@@ -320,7 +320,8 @@ class LocatorNet:
         """True when consecutive steps of an epoch may be chained (loc_train_step_chain: the layer-1 backward of step t
         also produces the layer-1 forward of step t + 1): width padding to 64 / 128 / 256 / 512, nlayers >= 2, batch <= 32 (<= 64 at
         width 256), Dropout not
-        on the BatchNorm output."""
+        on the BatchNorm output, and the chained kernel's 32-bit byte offsets into W1 / m / v (at most 4,194,272 padded SNPs,
+        2,097,120 at width 512)."""
         net = self._net or self.cnet()
         return bool(self.lib.loc_train_chain_supported(C.byref(net)))
 

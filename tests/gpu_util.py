@@ -56,3 +56,99 @@ def params_err(pa, pb):
         out[f"W{l}"] = maxerr(pa["W"][l], pb["W"][l])
         out[f"b{l}"] = maxerr(pa["b"][l], pb["b"][l])
     return out
+
+
+# ---------------------------------------------------------------- sparse-support problems (tests/test_gpu_large_k.py)
+# Only a few 32-SNP k-tiles carry real genotypes and keep their first-layer weights; every other SNP column is constant
+# over the samples (mostly 0, one tile of 1s and one of 2s) and its W1 row is zero.  There x - mean = 0 exactly, so those
+# columns add nothing to z1, their W1 / gamma / beta gradients are exactly 0 (dbeta_k = sum_h (sum_b dZ_bh) W1_kh) and
+# Adam leaves W1 / m / v / gamma / beta bit-for-bit where they were: the full problem trains exactly like the REDUCED one
+# made of the active columns alone (tests/test_oracle.py pins this on the oracle), which the fp64 oracle can afford at
+# millions of SNPs.  Nothing here builds a K x H array, on the device or the host.
+
+def sparse_problem(K, width, nlayers, active_tiles, n, seed):
+    """-> x (n, K) uint8, y (n, 2), cols (sorted active SNP columns < K), const {tile: value} of the 1s / 2s tiles.
+    Each active tile draws its own allele frequencies, so reading the wrong tile changes the numbers."""
+    rng = np.random.default_rng(seed)
+    nkt = (K + 31) // 32
+    tiles = sorted(set(int(t) for t in active_tiles))
+    assert tiles and tiles[0] >= 0 and tiles[-1] < nkt, (tiles, nkt)
+    x = np.zeros((n, K), np.uint8)
+    for kt in tiles:
+        k0, k1 = 32 * kt, min(32 * kt + 32, K)
+        af = rng.beta(0.4, 0.9, k1 - k0).clip(0.05, 0.95)
+        x[:, k0:k1] = rng.binomial(2, af, (n, k1 - k0))
+    free = [kt for kt in (2, 3, nkt - 2, nkt - 3) if 0 <= kt < nkt and kt not in tiles]
+    const = {free[0]: 1, free[-1]: 2} if len(free) >= 2 else {}
+    for kt, c in const.items():
+        x[:, 32 * kt:min(32 * kt + 32, K)] = c
+    cols = np.concatenate([np.arange(32 * kt, min(32 * kt + 32, K)) for kt in tiles])
+    xa = x[:, cols].astype(np.float64)
+    y = (xa - xa.mean(0)) @ (rng.normal(0, 1, (len(cols), 2)) / np.sqrt(len(cols)))
+    y = (y - y.mean(0)) / y.std(0)
+    return x, y, cols, const
+
+
+def keep_w1_tiles(net, tiles):
+    """Zero every W1 row of the device-initialised net except the k-tiles `tiles`: in the W1S layout k-tile kt is the
+    contiguous run of 32 * Hp floats at lay.w1 + kt * 32 * Hp, so the runs are saved, the section zeroed, the runs
+    written back."""
+    run = 32 * net.d.Hp
+    w1 = net.params[net.lay.w1:net.lay.w1 + net.d.Kp * net.d.Hp]
+    saved = [w1[kt * run:(kt + 1) * run].clone() for kt in tiles]
+    w1.zero_()
+    for kt, s in zip(tiles, saved):
+        w1[kt * run:(kt + 1) * run] = s
+    net.params_changed()
+
+
+def _w1s_tile_index(Hp):
+    """[32, Hp] offsets of (SNP kl, unit h) inside one k-tile's run of the W1S layout (loc_w1s_index with kt = 0)."""
+    kl, h = np.meshgrid(np.arange(32), np.arange(Hp), indexing="ij")
+    ht, hl = h >> 5, h & 31
+    q, hi, c = hl >> 3, (hl >> 2) & 1, hl & 3
+    return ((ht * 4 + q) * 256 + (hi * 32 + kl) * 4 + c).astype(np.int64)
+
+
+def read_w1_tiles(flat, lay, tiles, Hp):
+    """(32 * len(tiles), Hp) rows of W1 (or of its Adam moments: same layout) for the k-tiles `tiles`, in Keras
+    orientation, read from the flat device buffer tile by tile."""
+    run = 32 * Hp
+    idx = _w1s_tile_index(Hp)
+    out = [flat[lay.w1 + kt * run:lay.w1 + (kt + 1) * run].cpu().numpy()[idx] for kt in tiles]
+    return np.concatenate(out, 0)
+
+
+def export_reduced(net, flat, tiles, cols, with_moving=True):
+    """Oracle-format dict of the reduced problem from a flat device buffer (params, adam_m or adam_v): W[0] = the W1 rows
+    of the active SNPs `cols` (k-tiles `tiles`), gamma / beta / moving statistics at those SNPs; hidden layers and heads
+    straight from their small sections."""
+    d, lay = net.d, net.lay
+    rows = np.concatenate([np.arange(32 * kt, 32 * kt + 32) for kt in tiles])
+    keep = np.isin(rows, cols)
+    W = [read_w1_tiles(flat, lay, tiles, d.Hp)[keep][:, :d.H]]
+    b = [flat[lay.b1:lay.b1 + d.H].cpu().numpy()]
+    for i in range(d.L - 1):
+        W.append(flat[lay.wh + i * d.Hp * d.Hp:lay.wh + (i + 1) * d.Hp * d.Hp].view(d.Hp, d.Hp)[:d.H, :d.H].cpu().numpy())
+        b.append(flat[lay.bh + i * d.Hp:lay.bh + i * d.Hp + d.H].cpu().numpy())
+    W.append(flat[lay.wa:lay.wa + 2 * d.Hp].view(d.Hp, 2)[:d.H].cpu().numpy())
+    b.append(flat[lay.ba:lay.ba + 2].cpu().numpy())
+    W.append(flat[lay.wb:lay.wb + 4].view(2, 2).cpu().numpy())
+    b.append(flat[lay.bb:lay.bb + 2].cpu().numpy())
+    sel = torch.from_numpy(cols.astype(np.int64)).to(flat.device)
+    out = {"W": W, "b": b}
+    for k in ("gamma", "beta") + (("mov_mean", "mov_var") if with_moving else ()):
+        out[k] = flat[getattr(lay, k) + sel].cpu().numpy()
+    return out
+
+
+def untouched(section, tiles, value, per_tile, atol=0.0, chunk=1 << 26):
+    """Entries of `section` (a flat device view, per_tile entries per k-tile) OUTSIDE the k-tiles `tiles` that differ from
+    `value` by more than atol, counted on the device chunk by chunk (no copy of the section)."""
+    bad, start = 0, 0
+    for end in sorted(int(t) * per_tile for t in tiles) + [section.numel()]:
+        for a in range(start, end, chunk):
+            part = section[a:min(a + chunk, end)]
+            bad += int(((part != value) if atol == 0 else ((part - value).abs_() > atol)).sum().item())
+        start = max(start, end + per_tile)
+    return bad

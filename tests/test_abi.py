@@ -96,7 +96,7 @@ def test_codecs_library_loads_and_exports_its_entry_points(repo_root):
 def test_train_chain_supported_is_decided_by_shape_alone():
     """loc_train_chain_supported is host logic over the loc_net fields (no kernel, no device memory): width padding to
     64, 128, 256 or 512, at least one hidden layer, batch <= 32, Dropout not on the BatchNorm output, 16-byte row pitch, and the chained
-    kernel's 32-bit byte offsets (Kp * 1024 < 2^32: just under 4.2 million SNPs)."""
+    kernel's 32-bit byte offsets (Kp * max(Hp, 256) * 4 < 2^32: just under 4.2 million SNPs, 2.1 million at width 512)."""
     lib = _lib.load()
 
     def net(K=100000, width=256, nlayers=10, drop=0.25, slot_rows=32, pitch=None, wht=1, grid=512):
@@ -119,4 +119,6 @@ def test_train_chain_supported_is_decided_by_shape_alone():
     assert not ok(wht=None)                                          # no fused hidden stack
     assert not ok(pitch=100008)                                      # rows not 16-byte aligned
     assert ok(K=4194240) and not ok(K=4194304)                       # Kp * 1024 < 2^32
+    assert ok(width=512, K=2097120) and not ok(width=512, K=2097152)  # width 512: Kp * 2048 < 2^32
+    assert ok(width=128, K=4194240) and ok(width=64, K=4194240) and not ok(width=64, K=4194304)   # narrower: the width-256 limit
     assert ok(nlayers=3) and ok(nlayers=2, drop=0.25)                # Dropout after layer 1 is fine (n_pre = 1), only n_pre = 0 is not

@@ -217,3 +217,49 @@ def test_torch_cpu_restatement_matches_the_numpy_oracle():
         for l in range(len(pref["W"])):
             assert np.abs(got["W"][l] - pref["W"][l]).max() < 5e-5, (fused, l)
             assert np.abs(got["b"][l] - pref["b"][l]).max() < 5e-5, (fused, l)
+
+
+def test_sparse_support_problem_trains_like_its_reduced_problem():
+    """The premise of tests/test_gpu_large_k.py: SNP columns that are constant over the samples (0s, one tile of 1s, one
+    of 2s) and start with zero first-layer weights change nothing.  x - mean = 0 exactly there, so they add nothing to z1,
+    their W1 / gamma / beta gradients are exactly 0 and Adam leaves them where they were: a fit of the full problem equals
+    the fit of the problem made of the active columns alone, to fp64 round-off, with the same permutations and masks."""
+    from tests.gpu_util import sparse_problem
+    K, width, nlayers, n_train = 2000, 64, 4, 80
+    tiles = [0, 1, 30, 31, 62]                                     # tile 62 is the last one, 16 SNPs (K = 62 * 32 + 16)
+    x, y, cols, const = sparse_problem(K, width, nlayers, tiles, n_train + 20, seed=3)
+    assert sorted(const.values()) == [1, 2] and len(cols) == 4 * 32 + 16
+    rng = np.random.default_rng(4)
+    p = O.init_params(K, width, nlayers, rng)
+    inactive = np.setdiff1d(np.arange(K), cols)
+    p["W"][0][inactive] = 0.0
+    pr = O.copy_params(p)
+    pr["W"][0] = p["W"][0][cols]
+    for k in ("gamma", "beta", "mov_mean", "mov_var"):
+        pr[k] = p[k][cols]
+    perms = [np.random.default_rng(10 + e).permutation(n_train) for e in range(3)]
+    masks = [[rng.random((32, width)) >= 0.25 for _ in range(3)] for _ in range(3)]
+    tr, va = slice(0, n_train), slice(n_train, n_train + 20)
+    kw = dict(batch_size=32, max_epochs=3, patience=100, drop_p=0.25, perm_fn=lambda e: perms[e],
+              mask_fn=lambda e, s, nb: masks[e][s][:nb])
+    hf, _ = O.fit(p, x[tr], y[tr], x[va], y[va], **kw)
+    hr, _ = O.fit(pr, x[tr][:, cols], y[tr], x[va][:, cols], y[va], **kw)
+    assert len(hf["loss"]) == 3
+    assert np.abs(np.subtract(hf["loss"], hr["loss"])).max() < 1e-12
+    assert np.abs(np.subtract(hf["val_loss"], hr["val_loss"])).max() < 1e-12
+    assert np.abs(p["W"][0][cols] - pr["W"][0]).max() < 1e-12
+    w0 = O.init_params(K, width, nlayers, np.random.default_rng(4))["W"][0][cols]
+    assert np.abs(pr["W"][0] - w0).max() > 1e-4                    # the active rows did train
+    for l in range(1, nlayers + 2):
+        assert np.abs(p["W"][l] - pr["W"][l]).max() < 1e-12 and np.abs(p["b"][l] - pr["b"][l]).max() < 1e-12
+    for k in ("gamma", "beta", "mov_mean", "mov_var"):
+        assert np.abs(p[k][cols] - pr[k]).max() < 1e-12, k
+    assert not p["W"][0][inactive].any()
+    assert (p["gamma"][inactive] == 1.0).all() and (p["beta"][inactive] == 0.0).all()
+    # moving statistics of a constant column c after s = 9 steps: mean c (1 - 0.99^s), variance 0.99^s
+    c = np.zeros(K)
+    for kt, v in const.items():
+        c[32 * kt:32 * kt + 32] = v
+    assert np.abs(p["mov_mean"][inactive] - c[inactive] * (1 - 0.99 ** 9)).max() < 1e-12
+    assert np.abs(p["mov_var"][inactive] - 0.99 ** 9).max() < 1e-12
+    assert np.abs(O.predict(p, x) - O.predict(pr, x[:, cols])).max() < 1e-12
