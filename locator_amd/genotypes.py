@@ -23,8 +23,9 @@ import numpy as np
 
 
 # ------------------------------------------------------------------ VCF
-def _parse_gt_fast(fields, n):
-    """All calls are single-digit diploid 'a|b' / 'a/b' with GT the only (or first) FORMAT key."""
+def _parse_gt_fast(fields, n, seps=None):
+    """All calls are single-digit diploid 'a|b' / 'a/b' with GT the only (or first) FORMAT key.  seps: a list that gets
+    the separator bytes of the line (124 '|', 47 '/') appended."""
     s = "\t".join(fields)
     if len(s) != 4 * n - 1:
         return None
@@ -39,26 +40,44 @@ def _parse_gt_fast(fields, n):
         if not np.all(digit | (c == 46)):
             return None
         out[:, j] = np.where(digit, c.astype(np.int16) - 48, -1).astype(np.int8)
+    if seps is not None:
+        seps.append(sep)
     return out
 
 
-def _parse_gt_slow(fields, n):
+def _parse_gt_slow(fields, n, seps=None):
     out = np.full((n, 2), -1, np.int8)
+    sep = np.full(n, 124, np.uint8)
     for i, f in enumerate(fields):
-        gt = f.split(":", 1)[0].replace("|", "/").split("/")
+        raw = f.split(":", 1)[0]
+        if "/" in raw:
+            sep[i] = 47
+        gt = raw.replace("|", "/").split("/")
         for j, a in enumerate(gt[:2]):
             if a != "." and a != "":
                 out[i, j] = int(a)
         if len(gt) == 1:            # haploid call: second allele stays missing (-1), as allel pads
             out[i, 1] = -1
+    if seps is not None:
+        seps.append(sep)
     return out
 
 
-def read_vcf(path):
+def unphased_hets(gt, sep):
+    """Heterozygous calls written unphased: both alleles called, different, separator '/' (47).  gt (..., 2) int8,
+    sep (...) uint8 -> count."""
+    a, b = gt[..., 0], gt[..., 1]
+    return int(np.count_nonzero((sep == 47) & (a >= 0) & (b >= 0) & (a != b)))
+
+
+def read_vcf(path, phase=False):
     """Subset of allel.read_vcf used by locator.py:195-199: returns dict with 'calldata/GT'
-    (variants, samples, 2) int8, 'samples' (object array of str) and 'variants/POS' (int32)."""
+    (variants, samples, 2) int8, 'samples' (object array of str) and 'variants/POS' (int32).  phase=True (--phased) adds
+    'unphased_hets': the number of heterozygous calls written with '/' (their two alleles have no order)."""
     opener = gzip.open if str(path).endswith(".gz") else open
     samples, gts, pos = None, [], []
+    unphased = 0
+    seps = [] if phase else None
     with opener(path, "rt") as fh:
         for line in fh:
             if line.startswith("##"):
@@ -74,17 +93,46 @@ def read_vcf(path):
             fmt = f[8]
             g = None
             if fmt == "GT":
-                g = _parse_gt_fast(f[9:], n)
+                g = _parse_gt_fast(f[9:], n, seps)
             if g is None:
                 if fmt.split(":")[0] != "GT":
                     raise ValueError("VCF FORMAT must start with GT")
-                g = _parse_gt_slow(f[9:], n)
+                g = _parse_gt_slow(f[9:], n, seps)
+            if phase:
+                unphased += unphased_hets(g, seps.pop())
             gts.append(g)
             pos.append(int(f[1]))
     if samples is None:
         raise ValueError(f"{path}: no #CHROM header line")
     gt = np.stack(gts, axis=0) if gts else np.zeros((0, len(samples), 2), np.int8)
-    return {"calldata/GT": gt, "samples": samples, "variants/POS": np.asarray(pos, dtype=np.int32)}
+    out = {"calldata/GT": gt, "samples": samples, "variants/POS": np.asarray(pos, dtype=np.int32)}
+    if phase:
+        out["unphased_hets"] = unphased
+    return out
+
+
+def zarr_unphased_hets(callset):
+    """--phased on a zarr store: heterozygous calls flagged unphased by a `calldata/GT_phased` array (variants, samples)
+    of bools, as `allel.vcf_to_zarr` writes it when asked for that field.  None when the store has no such array or this
+    reader cannot read it (the store is then taken as phased).  Reads the flags a chunk of variants at a time and the
+    calls only where a flag is False."""
+    try:
+        ph = callset["calldata/GT_phased"]
+        if len(ph.shape) != 2 or np.dtype(ph.dtype) != np.bool_:
+            return None
+        gt = callset["calldata/GT"]
+        step = max(1, int(ph.chunks[0]))
+        n = 0
+        for a in range(0, ph.shape[0], step):
+            flags = np.asarray(ph[a:a + step])
+            if flags.all():
+                continue
+            g = np.asarray(gt[a:a + step])
+            het = (g[:, :, 0] >= 0) & (g[:, :, 1] >= 0) & (g[:, :, 0] != g[:, :, 1])
+            n += int(np.count_nonzero(het & ~flags))
+        return n
+    except (KeyError, ValueError, OSError, IndexError):
+        return None
 
 
 # ------------------------------------------------------------------ zarr v2 directory store
@@ -533,17 +581,27 @@ def is_missing(gt):
 
 
 def replace_md(gt, rng=np.random):
-    """locator.py:251-262: impute missing calls with Binomial(2, allele-1 frequency of the site), drawing
-    from the global legacy NumPy stream once per missing call in variant-major order."""
+    """locator.py:251-262: impute missing calls with Binomial(P, allele-1 frequency of the site), drawing
+    from the global legacy NumPy stream once per missing call in variant-major order.  P = gt.shape[2], the ploidy of
+    the calls: 2 for diploid genotypes (the reference's Binomial(2, dc / (2 n_called))), 1 for the haplotype view
+    (V, 2N, 1) of --phased, whose missing alleles get Binomial(1, dc / n_called) - 0 or 1."""
+    P = gt.shape[2]
     dc = count_alleles(gt, max(int(gt.max()), 1))[:, 1]
     ac = to_allele_counts_1(gt)
     missingness = is_missing(gt)
     ninds = (~missingness).sum(axis=1)
     with np.errstate(divide="ignore", invalid="ignore"):
-        af = dc / (2 * ninds)
+        af = dc / (P * ninds)
     for i, j in np.argwhere(missingness):
-        ac[i, j] = rng.binomial(2, af[i])
+        ac[i, j] = rng.binomial(P, af[i])
     return ac
+
+
+def haplotypes(gt):
+    """--phased: the calls (V, N, 2) viewed as (V, 2N, 1) - row 2s + h holds allele h of sample s (no copy).  Every filter
+    and count of this module then works on haplotype rows: to_allele_counts_1 gives 1 where the allele is 1, else 0."""
+    V, N, P = gt.shape
+    return gt.reshape(V, N * P, 1)
 
 
 HOST_THREADS = 8      # threads of the C passes below (they release the GIL)

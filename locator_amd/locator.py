@@ -19,7 +19,8 @@ Deliberate, documented deviations:
   * --batch_size is limited to 4096 rows (the reference default is 32; above 32 it needs a --width that pads to 64,
     128 or 256 and --nlayers >= 4 with dropout; above 128 the step is correct but not tuned) and --width to 1024 (above 512: per-layer kernels);
   * extra flags --gpus / --fits_per_gpu / --unit_timeout / --no_graph / --no_chain / --net_seed / --load_weights / --predict_mode / --predict_packed / --predict_pieces (recorded at
-    the end of params.json).
+    the end of params.json), and --phased (one prediction per haplotype of phased calls, after scripts/locator_phased.py;
+    recorded in params.json only when given).
 """
 from __future__ import annotations
 
@@ -128,6 +129,10 @@ def build_parser():
     p.add_argument("--net_seed", default=None, type=int,
                    help="seed of weight init / shuffling / dropout (the reference leaves these unseeded); "
                         "default: --seed, else entropy")
+    # absent from the namespace unless given: a run without it writes the same params.json as before the flag existed
+    p.add_argument("--phased", default=argparse.SUPPRESS, action="store_true",
+                   help="phased calls (--vcf / --zarr): one row and one predicted location per haplotype, IDs <id>_h0 / "
+                        "<id>_h1; both haplotypes of an individual fall in the same train / validation / prediction set")
     return p
 
 
@@ -166,6 +171,53 @@ def _write_atomic(path, writer, mode="w"):
     os.replace(tmp, path)
 
 
+def _phased(a=None):
+    return bool(getattr(args if a is None else a, "phased", False))
+
+
+def row_ids(samples):
+    """The IDs of the matrix rows: the samples, or with --phased `<id>_h0`, `<id>_h1` per sample in row order 2s + h."""
+    if not _phased():
+        return samples
+    return np.array([f"{s}_h{h}" for s in np.asarray(samples).astype(str) for h in (0, 1)], dtype=object)
+
+
+def haplotype_rows(idx):
+    """Individual indices -> their haplotype rows 2s, 2s + 1, in the individuals' order."""
+    idx = np.asarray(idx, dtype=np.int64)
+    return (2 * idx[:, None] + np.arange(2, dtype=np.int64)).reshape(-1)
+
+
+_PRELOADED = None      # (path, gt, samples) of a VCF that _phased_preflight has already read for the prologue
+
+
+def _phased_preflight():
+    """--phased refusals, before any worker or device starts: a count matrix carries no phase; a VCF or a zarr store
+    (when it has a readable calldata/GT_phased) must have no heterozygous call without phase.  The VCF read here is kept
+    for the prologue."""
+    global _PRELOADED
+    _PRELOADED = None
+    if not _phased():
+        return
+    if args.matrix is not None and args.vcf is None and args.zarr is None:
+        raise SystemExit("--phased needs --vcf or --zarr: an allele-count --matrix carries no phase")
+    if args.zarr is not None:
+        n = G.zarr_unphased_hets(G.open_group(args.zarr, mode="r"))
+        where = f"{args.zarr}: calldata/GT_phased"
+    elif args.vcf is not None:
+        print("reading VCF")
+        vcf = G.read_vcf(args.vcf, phase=True)
+        n = vcf["unphased_hets"]
+        where = args.vcf
+    else:
+        return
+    if n:
+        raise SystemExit(f"--phased: {where} has {n} heterozygous call(s) without phase (written 'a/b'); "
+                         "phase them first or run without --phased")
+    if args.zarr is None:
+        _PRELOADED = (args.vcf, vcf["calldata/GT"], vcf["samples"])
+
+
 # ------------------------------------------------------------------ ingest (locator.py:187-308)
 def load_genotypes():
     """(variants, samples, 2) int8 calls and the sample IDs from whichever of --zarr / --vcf / --matrix was given
@@ -181,6 +233,10 @@ def load_genotypes():
             gt = np.asarray(za[:], dtype=np.int8)
         return gt, np.asarray(callset["samples"][:])
     if args.vcf is not None:
+        global _PRELOADED
+        loaded, _PRELOADED = _PRELOADED, None
+        if loaded is not None and loaded[0] == args.vcf:
+            return loaded[1], loaded[2]
         print("reading VCF")
         vcf = G.read_vcf(args.vcf)
         return vcf["calldata/GT"], vcf["samples"]
@@ -200,7 +256,11 @@ def sort_samples(samples, genotypes):
         print("sample ordering failed! Check that sample IDs match the VCF.")
         sys.exit()
     locs = sample_data[["x", "y"]].to_numpy()
-    print("loaded " + str(np.shape(genotypes)) + " genotypes\n\n")
+    if _phased():
+        V, N = np.shape(genotypes)[:2]
+        print(f"loaded ({V}, {2 * N}, 1) haplotypes of {N} individuals\n\n")
+    else:
+        print("loaded " + str(np.shape(genotypes)) + " genotypes\n\n")
     return sample_data, locs
 
 
@@ -210,6 +270,10 @@ def replace_md(genotypes):
 
 
 def filter_snps(genotypes):
+    """--phased: the same filters on the haplotype view (V, 2N, 1): the same sites pass, the matrix holds 0/1 per
+    haplotype row."""
+    if _phased():
+        genotypes = G.haplotypes(genotypes)
     return G.filter_snps(genotypes, min_mac=args.min_mac, max_snps=args.max_SNPs,
                          impute_missing=args.impute_missing)
 
@@ -232,9 +296,28 @@ def split_indices(locs, train_split):
     return train, test, pred
 
 
+def row_locs(samples, genotypes):
+    """sort_samples + normalize_locs -> (meanlong, sdlong, meanlat, sdlat, z-scored coordinates per matrix row).  --phased:
+    the individuals' coordinates are normalised (duplicating rows would change neither mean nor SD) and then given to
+    both haplotype rows."""
+    sample_data, locs = sort_samples(samples, genotypes)
+    meanlong, sdlong, meanlat, sdlat, locs = normalize_locs(locs)
+    if _phased():
+        locs = np.repeat(locs, 2, axis=0)
+    return meanlong, sdlong, meanlat, sdlat, locs
+
+
+def split_rows(locs, train_split):
+    """split_indices over the matrix rows.  --phased: the one np.random.choice is drawn over the located INDIVIDUALS
+    (locs[0::2]) - the same draw as an unphased run - and each chosen individual becomes its two haplotype rows."""
+    if not _phased():
+        return split_indices(locs, train_split)
+    return tuple(haplotype_rows(idx) for idx in split_indices(locs[0::2], train_split))
+
+
 def split_train_test(ac, locs):
     """locator.py:295-308: row sets from split_indices, genotypes as sample-major matrices."""
-    train, test, pred = split_indices(locs, args.train_split)
+    train, test, pred = split_rows(locs, args.train_split)
     rows = lambda idx: G.rows_transposed(ac, idx) if len(idx) else np.zeros((0, ac.shape[0]), ac.dtype)
     return train, test, rows(train), rows(test), locs[train], locs[test], pred, rows(pred)
 
@@ -457,6 +540,8 @@ def predict_locs(model, predgen, sdlong, meanlong, sdlat, meanlat, testlocs, pre
         fitted = _to_map_units(z_val, sdlong, meanlong, sdlat, meanlat)
         dists = np.sqrt(((fitted - truth) ** 2).sum(axis=1)).tolist()
         if verbose:
+            if _phased():
+                print(f"validation on {len(dists)} haplotypes ({len(dists) // 2} individuals)")
             r2 = [np.corrcoef(fitted[:, a], truth[:, a])[0][1] ** 2 for a in (0, 1)]
             print(f"R2(x)={r2[0]}\nR2(y)={r2[1]}\nmean validation error {np.mean(dists)}\n"
                   f"median validation error {np.median(dists)}\n")
@@ -628,6 +713,8 @@ def _fit_unit_body(unit, device="cuda:0"):
         nbytes = int(np.prod(shape, dtype=np.int64))
         pin = unit.pop("gt_pin")
         gt_dev = pin[:nbytes].to(device, non_blocking=True).view(torch.int8).view(*shape)
+        if unit.get("phased"):
+            gt_dev = gt_dev.view(shape[0], shape[1] * shape[2], 1)        # [variants][2N haplotypes][1]
         train, test, pred = unit["train"], unit["test"], unit["pred"]
         order = np.concatenate([np.asarray(train), np.asarray(test), np.asarray(pred)]).astype(np.int32)
         X, K = filter_snps_device(gt_dev, order, args.min_mac)
@@ -758,41 +845,46 @@ def _window_units(samples, lazy=None):
     if lazy is None:
         lazy = not args.impute_missing and args.max_SNPs is None
     units = []
+    ids = row_ids(samples)
     for n, (i, size, a, b) in enumerate(_window_bounds()):
         print(f"\nProcessing window {i}-{i + size}")
         print(f"SNPs {a}-{b}")
         unit = dict(name=f"window {i}-{i + size - 1}", replicate=n, boot=None, out=f"{args.out}_{i}-{i + size - 1}",
-                    samples=samples)
+                    samples=ids)
+        if _phased():
+            unit["phased"] = True           # rows are haplotypes: the window's calls are viewed as (V, 2N, 1)
         if lazy:
             class _Shape:
                 shape = (b - a, len(samples), 2)
-            sample_data, locs = sort_samples(samples, _Shape())
-            meanlong, sdlong, meanlat, sdlat, locs = normalize_locs(locs)
-            train, test, pred = split_indices(locs, args.train_split)
+            meanlong, sdlong, meanlat, sdlat, locs = row_locs(samples, _Shape())
+            train, test, pred = split_rows(locs, args.train_split)
             unit.update(window=(a, b), zarr=args.zarr, train=train, test=test, pred=pred, locs=locs,
                         sdlong=sdlong, meanlong=meanlong, sdlat=sdlat, meanlat=meanlat)
         else:
             unit.update(window=(a, b), zarr=args.zarr)
-            _load_window(unit, draw_split=True)
+            _load_window(unit, draw_split=True, individuals=samples)
         units.append(unit)
     return units
 
 
-def _load_window(unit, draw_split=False):
+def _load_window(unit, draw_split=False, individuals=None):
     """Slice the store (gt[a:b]: excludes SNP b, as the reference does), filter, and cut the
-    train / validation / prediction rows.  Runs in the worker for lazy units."""
+    train / validation / prediction rows.  Runs in the worker for lazy units.  individuals: the sample IDs of the store
+    (the eager path's sort_samples; unit["samples"] are the row IDs)."""
     if "traingen" in unit:
         return unit
     a, b = unit["window"]
     gt = G.open_group(unit["zarr"], mode="r")["calldata/GT"]
     genotypes = np.asarray(gt[a:b, :, :], dtype=np.int8)
     if draw_split:                                   # eager path: reference order sort -> normalise -> filter -> split
-        sample_data, locs = sort_samples(unit["samples"], genotypes)
-        meanlong, sdlong, meanlat, sdlat, locs = normalize_locs(locs)
+        meanlong, sdlong, meanlat, sdlat, locs = row_locs(unit["samples"] if individuals is None else individuals,
+                                                          genotypes)
         ac = filter_snps(genotypes)
-        train, test, pred = split_indices(locs, args.train_split)
+        train, test, pred = split_rows(locs, args.train_split)
         unit.update(sdlong=sdlong, meanlong=meanlong, sdlat=sdlat, meanlat=meanlat)
     else:
+        if unit.get("phased"):
+            genotypes = G.haplotypes(genotypes)
         ac = G.filter_snps(genotypes, min_mac=unit["args"].min_mac if "args" in unit else args.min_mac, verbose=False)
         train, test, pred, locs = unit["train"], unit["test"], unit["pred"], unit["locs"]
     unit.update(traingen=G.rows_transposed(ac, train), testgen=G.rows_transposed(ac, test),
@@ -819,7 +911,8 @@ def _bootstrap_units(n_sites):
 
 def _prologue(force_full=False):
     """locator.py:507-516.  Returns (samples, state) where state is None in the windows fast path or the
-    tuple (meanlong, sdlong, meanlat, sdlat, ac, train, test, traingen, testgen, trainlocs, testlocs, pred, predgen)."""
+    tuple (meanlong, sdlong, meanlat, sdlat, ac, train, test, traingen, testgen, trainlocs, testlocs, pred, predgen).
+    samples are the store's sample IDs; with --phased every row index of state is a haplotype row (row_ids)."""
     if args.windows and not args.impute_missing and args.max_SNPs is None and not force_full:
         # The reference loads and filters the WHOLE store here (locator.py:508-516) and then discards the
         # result: the window loop re-slices, re-filters and re-splits.  All that survives is the state of
@@ -833,11 +926,10 @@ def _prologue(force_full=False):
             shape = tuple(callset["calldata/GT"].shape)
         sample_data, locs = sort_samples(samples, _Shape())
         meanlong, sdlong, meanlat, sdlat, locs = normalize_locs(locs)
-        split_indices(locs, args.train_split)
+        split_indices(locs, args.train_split)        # --phased: the same draw (over individuals)
         return samples, None
     genotypes, samples = load_genotypes()
-    sample_data, locs = sort_samples(samples, genotypes)
-    meanlong, sdlong, meanlat, sdlat, locs = normalize_locs(locs)
+    meanlong, sdlong, meanlat, sdlat, locs = row_locs(samples, genotypes)
     ac = filter_snps(genotypes)
     train, test, traingen, testgen, trainlocs, testlocs, pred, predgen = split_train_test(ac, locs)
     return samples, (meanlong, sdlong, meanlat, sdlat, ac, train, test, traingen, testgen, trainlocs, testlocs,
@@ -884,6 +976,7 @@ def main(argv=None):
         # prologue, and every worker is then a fork + one device context (replicates.warm_start)
         replicates.warm_start("forkserver")
     _setup(argv)
+    _phased_preflight()
 
     pool = None
     if args.windows or args.bootstrap:
@@ -927,7 +1020,7 @@ def _main_body(pool, t_program):
             plot_history(_H(results[-1]["history"]), results[-1]["dists"])
     elif not args.bootstrap and not args.jacknife:
         unit = dict(name="single", replicate=0, boot=0, out=args.out, traingen=traingen, testgen=testgen,
-                    predgen=predgen, trainlocs=trainlocs, testlocs=testlocs, pred=pred, samples=samples,
+                    predgen=predgen, trainlocs=trainlocs, testlocs=testlocs, pred=pred, samples=row_ids(samples),
                     sdlong=sdlong, meanlong=meanlong, sdlat=sdlat, meanlat=meanlat, args=args)
         r = _fit_unit(unit, reraise=True)
         plot_history(_H(r["history"]), r["dists"])
@@ -935,7 +1028,7 @@ def _main_body(pool, t_program):
         units = _bootstrap_units(traingen.shape[1])
         shared = dict(traingen=np.ascontiguousarray(traingen), testgen=np.ascontiguousarray(testgen),
                       predgen=np.ascontiguousarray(predgen), trainlocs=trainlocs, testlocs=testlocs, pred=pred,
-                      samples=samples, sdlong=sdlong, meanlong=meanlong, sdlat=sdlat, meanlat=meanlat, out=args.out)
+                      samples=row_ids(samples), sdlong=sdlong, meanlong=meanlong, sdlat=sdlat, meanlat=meanlat, out=args.out)
         results = pool.run(units, shared)
         _print_replicate_summary(pool, results, t_program)
         failed = sum("error" in r for r in results)
@@ -947,25 +1040,25 @@ def _main_body(pool, t_program):
             _write_atomic(args.out + "_history.txt", lambda fh: last.to_csv(fh, sep="\t", index=False))
             plot_history(_H(results[-1]["history"]), results[-1]["dists"])
     elif args.jacknife:
-        _jacknife(ac, traingen, testgen, trainlocs, testlocs, predgen, pred, samples, sdlong, meanlong, sdlat, meanlat)
+        _jacknife(ac, traingen, testgen, trainlocs, testlocs, predgen, pred, row_ids(samples), sdlong, meanlong, sdlat, meanlat)
     if failed:
         print(f"{failed} replicate fit(s) FAILED", file=sys.stderr)
         return 1
     return 0
 
 
-def jacknife_draws(predgen, af, nboots, prop):
+def jacknife_draws(predgen, af, nboots, prop, ploidy=2):
     """The reference's jacknife randomness (locator.py:713-727), replicate after replicate from the global NumPy
     stream: the sites to redraw (choice without replacement), then for each of them, in that order, one
-    Binomial(2, site frequency) per prediction sample.  The per-site calls of the reference are issued as ONE
-    broadcast call per replicate: the legacy generator fills a broadcast request element by element in row-major
-    order through the same scalar routine, so the stream - and every value - is the same (tests/test_host.py).
+    Binomial(ploidy, site frequency) per prediction sample (ploidy 1: the 0/1 rows of --phased).  The per-site calls of
+    the reference are issued as ONE broadcast call per replicate: the legacy generator fills a broadcast request element
+    by element in row-major order through the same scalar routine, so the stream - and every value - is the same (tests/test_host.py).
     Returns [(sites, values[n_sites][n_pred])]."""
     n_pred, K = predgen.shape
     out = []
     for _ in range(nboots):
         sites = np.random.choice(K, int(K * prop), replace=False)
-        vals = np.random.binomial(2, np.asarray(af)[sites][:, None], (len(sites), n_pred)) if len(sites) else \
+        vals = np.random.binomial(ploidy, np.asarray(af)[sites][:, None], (len(sites), n_pred)) if len(sites) else \
             np.zeros((0, n_pred), np.int64)
         out.append((sites, vals))
     return out
@@ -987,8 +1080,12 @@ def _jacknife(ac, traingen, testgen, trainlocs, testlocs, predgen, pred, samples
     n_pred = base.shape[0]
     if n_pred == 0 or args.nboots < 1:
         return
-    af = ac.sum(axis=1) / (ac.shape[1] * 2)
-    draws = jacknife_draws(base, af, args.nboots, args.jacknife_prop)
+    if _phased():                                         # 0/1 haplotype rows: frequency over n_rows alleles, Binomial(1, af)
+        af = ac.sum(axis=1) / ac.shape[1]
+        draws = jacknife_draws(base, af, args.nboots, args.jacknife_prop, ploidy=1)
+    else:
+        af = ac.sum(axis=1) / (ac.shape[1] * 2)
+        draws = jacknife_draws(base, af, args.nboots, args.jacknife_prop)
     ids = np.asarray(samples)[pred]
     group = max(1, int(2e9 // max(1, base.size)))          # replicates per upload: at most ~2 GB of host staging
     for b0 in range(0, args.nboots, group):

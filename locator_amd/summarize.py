@@ -10,7 +10,8 @@ Reference: /root/reference/locator_py/plot_locator.py:26-44, :59-126 and scripts
                density evaluated at the predictions themselves (sklearn KernelDensity.score_samples in
                the reference, plot_locator.py:26-37); falls back to the mean if the estimate fails
 
-and, when the sample file has known coordinates, the error of both summaries.  Output
+and, when the sample file has known coordinates, the error of both summaries (a --phased row `<id>_h0` / `<id>_h1` that the
+sample file does not list is scored against `<id>`'s coordinates; its two haplotypes stay separate rows).  Output
 `{out}_centroids.txt` is tab-separated with the reference's columns sampleID, x, y, kd_x, kd_y, gc_x, gc_y
 (plot_locator.py:117-119).  Plotting itself is out of scope.
 
@@ -96,8 +97,11 @@ def summarize(indir, sample_data=None, out=None, bandwidth=0.2, silence=False, h
             kx, ky = kde_peak(xs, ys, bandwidth)
             gx, gy = centroid(xs, ys)
         tx = ty = np.nan
-        if truth is not None and sid in truth.index:
-            tx, ty = float(truth.loc[sid, "x"]), float(truth.loc[sid, "y"])
+        key = sid
+        if truth is not None and sid not in truth.index and str(sid)[-3:] in ("_h0", "_h1"):
+            key = str(sid)[:-3]                 # a --phased haplotype row: the truth is its individual's
+        if truth is not None and key in truth.index:
+            tx, ty = float(truth.loc[key, "x"]), float(truth.loc[key, "y"])
         rows.append({"sampleID": sid, "x": tx, "y": ty, "kd_x": kx, "kd_y": ky, "gc_x": gx, "gc_y": gy})
     bp = pd.DataFrame(rows, columns=["sampleID", "x", "y", "kd_x", "kd_y", "gc_x", "gc_y"])
     if out is not None:
