@@ -557,6 +557,16 @@ int loc_filter_snps_flags(const int8_t* gt, int64_t n_variants, int n_samples, i
 int loc_filter_snps_rows(const int8_t* gt, int64_t n_variants, int n_samples, int ploidy, const uint8_t* keep,
                          const int32_t* pos, const int32_t* sample_order, int n_out, uint8_t* X, int64_t x_pitch, void* stream);
 
+/* ---- a kept model on a new genotype file (python -m locator_amd.predict; locator_amd/query.py matches the sites) ----
+ * gt: the query's calls int8 [n_variants][n_samples][ploidy] (negative = missing); col_variant[k]: the query variant of model
+ * column k, or -1 (absent); col_allele[k]: the allele of that variant the column counts (1, or 0 for a REF/ALT swap, 2.. for
+ * a multi-allelic record).  X[r][k] = number of copies of col_allele[k] among the alleles of sample sample_order[r] at
+ * variant col_variant[k] (missing alleles count 0), and 0 for an absent column; r < n_out, k < K.  X is [n_out][x_pitch]
+ * uint8; columns K .. x_pitch are not written (the caller zeroes them).  A --phased model runs on the (V, 2N, 1) view. */
+int loc_query_rows(const int8_t* gt, int64_t n_variants, int n_samples, int ploidy, const int32_t* col_variant,
+                   const int8_t* col_allele, int K, const int32_t* sample_order, int n_out, uint8_t* X, int64_t x_pitch,
+                   void* stream);
+
 /* ---- the three callbacks of a fit, on the device (locator.py:330-362) ----
  * State of ModelCheckpoint(best only) -> EarlyStopping -> ReduceLROnPlateau, all on val_loss, strict '<', min_delta 0.
  * The host fills it once (bests = +inf, waits 0, lr = the fit's starting rate, epoch 0, stopped 0, stop_epoch / best_epoch

@@ -152,6 +152,7 @@ SIGNATURES = {
     "loc_predict_image_mode": (C.c_int, [C.POINTER(Net), C.c_int]),
     "loc_filter_snps_flags": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "loc_filter_snps_rows": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int64, vp]),
+    "loc_query_rows": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int64, vp]),
     "loc_epoch_callbacks": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
     "loc_snapshot_if": (C.c_int, [vp, vp, vp, C.c_int64, vp]),
     "loc_event_create": (C.c_int, [C.POINTER(vp)]),

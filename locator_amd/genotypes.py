@@ -70,12 +70,15 @@ def unphased_hets(gt, sep):
     return int(np.count_nonzero((sep == 47) & (a >= 0) & (b >= 0) & (a != b)))
 
 
-def read_vcf(path, phase=False):
+def read_vcf(path, phase=False, sites=False):
     """Subset of allel.read_vcf used by locator.py:195-199: returns dict with 'calldata/GT'
     (variants, samples, 2) int8, 'samples' (object array of str) and 'variants/POS' (int32).  phase=True (--phased) adds
-    'unphased_hets': the number of heterozygous calls written with '/' (their two alleles have no order)."""
+    'unphased_hets': the number of heterozygous calls written with '/' (their two alleles have no order).  sites=True
+    (--keep_model, locator_amd.predict) adds 'variants/CHROM' and 'variants/REF' (object arrays of str) and 'variants/ALT'
+    (variants, max ALT count) object array of str padded with '' as allel lays it out."""
     opener = gzip.open if str(path).endswith(".gz") else open
     samples, gts, pos = None, [], []
+    chrom, ref, alt = [], [], []
     unphased = 0
     seps = [] if phase else None
     with opener(path, "rt") as fh:
@@ -102,12 +105,23 @@ def read_vcf(path, phase=False):
                 unphased += unphased_hets(g, seps.pop())
             gts.append(g)
             pos.append(int(f[1]))
+            if sites:
+                chrom.append(f[0])
+                ref.append(f[3])
+                alt.append([] if f[4] == "." else f[4].split(","))
     if samples is None:
         raise ValueError(f"{path}: no #CHROM header line")
     gt = np.stack(gts, axis=0) if gts else np.zeros((0, len(samples), 2), np.int8)
     out = {"calldata/GT": gt, "samples": samples, "variants/POS": np.asarray(pos, dtype=np.int32)}
     if phase:
         out["unphased_hets"] = unphased
+    if sites:
+        out["variants/CHROM"] = np.array(chrom, dtype=object)
+        out["variants/REF"] = np.array(ref, dtype=object)
+        table = np.full((len(alt), max([1] + [len(a) for a in alt])), "", dtype=object)
+        for i, a in enumerate(alt):
+            table[i, :len(a)] = a
+        out["variants/ALT"] = table
     return out
 
 
@@ -519,8 +533,9 @@ def write_zarr_array(path, arr, chunks, compressor=None):
             fh.write(raw)
 
 
-def write_callset_zarr(path, gt, pos, samples, chunk_variants=65536, compressor=None):
-    """Synthetic `allel.vcf_to_zarr`-shaped store: calldata/GT, variants/POS, samples."""
+def write_callset_zarr(path, gt, pos, samples, chunk_variants=65536, compressor=None, chrom=None, ref=None, alt=None):
+    """Synthetic `allel.vcf_to_zarr`-shaped store: calldata/GT, variants/POS, samples, and variants/CHROM / REF / ALT
+    (fixed-width unicode; ALT may be 2-D, one column per alternate allele) when given."""
     os.makedirs(path, exist_ok=True)
     for g in ("", "calldata", "variants"):
         os.makedirs(os.path.join(path, g), exist_ok=True)
@@ -531,6 +546,48 @@ def write_callset_zarr(path, gt, pos, samples, chunk_variants=65536, compressor=
     write_zarr_array(os.path.join(path, "variants", "POS"), np.asarray(pos, np.int32), (chunk_variants,), compressor)
     s = np.asarray(samples)
     write_zarr_array(os.path.join(path, "samples"), s.astype("U"), (len(s),), None)
+    for name, col in (("CHROM", chrom), ("REF", ref), ("ALT", alt)):
+        if col is not None:
+            col = np.asarray(col).astype("U")
+            write_zarr_array(os.path.join(path, "variants", name), col, (chunk_variants,) + col.shape[1:], compressor)
+
+
+def zarr_sites(callset):
+    """variants/CHROM, POS, REF, ALT of a zarr store (allel.vcf_to_zarr layout; ALT (variants, numalt) or 1-D) as the dict
+    read_vcf(sites=True) returns.  Raises KeyError naming the first array the store lacks."""
+    out = {}
+    for name in ("CHROM", "POS", "REF", "ALT"):
+        try:
+            a = np.asarray(callset["variants/" + name][:])
+        except KeyError:
+            raise KeyError(f"variants/{name}") from None
+        if name == "POS":
+            out["variants/POS"] = a.astype(np.int64)
+            continue
+        a = a.astype(str).astype(object)
+        if name == "ALT" and a.ndim == 1:
+            a = a[:, None]
+        out["variants/" + name] = a
+    return out
+
+
+def matrix_sites(path):
+    """The column names of a --matrix file after 'sampleID': the identities of its sites."""
+    opener = gzip.open if str(path).endswith(".gz") else open
+    with opener(path, "rt") as fh:
+        header = fh.readline().rstrip("\n").split("\t")
+    return np.array([h.strip('"') for h in header if h.strip('"') != "sampleID"], dtype=object)
+
+
+def site_af(gt, idx, chunk=65536):
+    """Allele-1 frequency over the called alleles of every row, of the variants gt[idx] (the kept sites of a fit)."""
+    idx = np.asarray(idx, dtype=np.int64)
+    out = np.zeros(len(idx), np.float64)
+    for a in range(0, len(idx), chunk):
+        g = np.asarray(gt[idx[a:a + chunk]]).reshape(min(chunk, len(idx) - a), -1)
+        called = np.count_nonzero(g >= 0, axis=1)
+        out[a:a + chunk] = np.count_nonzero(g == 1, axis=1) / np.maximum(called, 1)
+    return out
 
 
 # ------------------------------------------------------------------ tab-delimited count matrix
@@ -652,29 +709,34 @@ def rows_transposed(ac, rows):
     return out
 
 
-def filter_snps(gt, min_mac=2, max_snps=None, impute_missing=False, rng=np.random, verbose=True, native=True):
+def filter_snps(gt, min_mac=2, max_snps=None, impute_missing=False, rng=np.random, verbose=True, native=True, sites=False):
     """locator.py:265-281: biallelic sites -> allele-1 count >= min_mac (skipped when min_mac == 1) ->
     allele-1 count matrix (sites x samples) -> optional random subset of max_SNPs sites.
     Quirks kept: the count filtered on is allele 1's, not the minor allele's; monomorphic
     sites never pass (Q8).  native: the two filters and the allele counts as C passes (same integers; the NumPy spelling
-    below stays as their restatement and as the --impute_missing path, whose draws follow the filtered array)."""
+    below stays as their restatement and as the --impute_missing path, whose draws follow the filtered array).  sites=True:
+    (matrix, index of the input variant of every row) - the same draws, nothing more (--keep_model)."""
     if verbose:
         print("filtering SNPs")
     if native and not impute_missing and np.ndim(gt) == 3 and gt.shape[0] > 0 and int(np.min(gt.shape)) > 0:
-        ac, _ = _filter_snps_native(gt, min_mac)
+        ac, keep = _filter_snps_native(gt, min_mac)
+        idx = np.flatnonzero(keep)
         if max_snps is not None:
-            ac = ac[rng.choice(range(ac.shape[0]), max_snps, replace=False), :]
+            pick = rng.choice(range(ac.shape[0]), max_snps, replace=False)
+            ac, idx = ac[pick, :], idx[pick]
         if verbose:
             print("running on " + str(len(ac)) + " genotypes after filtering\n\n\n")
-        return ac
+        return (ac, idx) if sites else ac
     tmp = count_alleles(gt)
-    gt = gt[is_biallelic(tmp)]
+    idx = np.flatnonzero(is_biallelic(tmp))
+    gt = gt[idx]
     if not min_mac == 1:
         derived = count_alleles(gt, max(int(gt.max()) if gt.size else 1, 1))[:, 1]
-        gt = gt[derived >= min_mac]
+        gt, idx = gt[derived >= min_mac], idx[derived >= min_mac]
     ac = replace_md(gt, rng) if impute_missing else to_allele_counts_1(gt)
     if max_snps is not None:
-        ac = ac[rng.choice(range(ac.shape[0]), max_snps, replace=False), :]
+        pick = rng.choice(range(ac.shape[0]), max_snps, replace=False)
+        ac, idx = ac[pick, :], idx[pick]
     if verbose:
         print("running on " + str(len(ac)) + " genotypes after filtering\n\n\n")
-    return ac
+    return (ac, idx) if sites else ac

@@ -19,8 +19,9 @@ Deliberate, documented deviations:
   * --batch_size is limited to 4096 rows (the reference default is 32; above 32 it needs a --width that pads to 64,
     128 or 256 and --nlayers >= 4 with dropout; above 128 the step is correct but not tuned) and --width to 1024 (above 512: per-layer kernels);
   * extra flags --gpus / --fits_per_gpu / --unit_timeout / --no_graph / --no_chain / --net_seed / --load_weights / --predict_mode / --predict_packed / --predict_pieces (recorded at
-    the end of params.json), and --phased (one prediction per haplotype of phased calls, after scripts/locator_phased.py;
-    recorded in params.json only when given).
+    the end of params.json), --phased (one prediction per haplotype of phased calls, after scripts/locator_phased.py) and
+    --keep_model (a {stem}.model.npz that `python -m locator_amd.predict` applies to new genotypes), both recorded in
+    params.json only when given.
 """
 from __future__ import annotations
 
@@ -133,16 +134,21 @@ def build_parser():
     p.add_argument("--phased", default=argparse.SUPPRESS, action="store_true",
                    help="phased calls (--vcf / --zarr): one row and one predicted location per haplotype, IDs <id>_h0 / "
                         "<id>_h1; both haplotypes of an individual fall in the same train / validation / prediction set")
+    p.add_argument("--keep_model", default=argparse.SUPPRESS, action="store_true",
+                   help="write {stem}.model.npz next to where --keep_weights writes {stem}.weights.npz: the weights plus the "
+                        "site (CHROM, POS, REF, ALT) of every input column, the coordinate normalisation and the run's "
+                        "parameters - what `python -m locator_amd.predict` needs to place new samples without training")
     return p
 
 
 args = None          # module-level namespace, as in the reference (locator.py:167)
+_PARAMS_TEXT = None  # the text of {out}_params.json (kept in every --keep_model file)
 
 
 def _setup(argv=None):
     """Parse flags, honour --seed / --gpu_number / --load_params and record the run in {out}_params.json
     (what the reference does at import time, locator.py:169-184, and again at the top of main, :490-505)."""
-    global args
+    global args, _PARAMS_TEXT
     parser = build_parser()
     args = parser.parse_args(argv)
     if args.load_params is not None:            # every value comes from the file; keys it lacks keep their defaults
@@ -156,6 +162,7 @@ def _setup(argv=None):
         for var in ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
             os.environ[var] = args.gpu_number
     _write_atomic(args.out + "_params.json", lambda fh: json.dump(vars(args), fh, indent=2))
+    _PARAMS_TEXT = json.dumps(vars(args), indent=2)
     seed = args.net_seed if args.net_seed is not None else args.seed
     args._net_seed = seed if seed is not None else int.from_bytes(os.urandom(4), "little")
     return args
@@ -173,6 +180,10 @@ def _write_atomic(path, writer, mode="w"):
 
 def _phased(a=None):
     return bool(getattr(args if a is None else a, "phased", False))
+
+
+def _keep_model(a=None):
+    return bool(getattr(args if a is None else a, "keep_model", False))
 
 
 def row_ids(samples):
@@ -206,7 +217,7 @@ def _phased_preflight():
         where = f"{args.zarr}: calldata/GT_phased"
     elif args.vcf is not None:
         print("reading VCF")
-        vcf = G.read_vcf(args.vcf, phase=True)
+        vcf = G.read_vcf(args.vcf, phase=True, sites=_keep_model())
         n = vcf["unphased_hets"]
         where = args.vcf
     else:
@@ -215,13 +226,16 @@ def _phased_preflight():
         raise SystemExit(f"--phased: {where} has {n} heterozygous call(s) without phase (written 'a/b'); "
                          "phase them first or run without --phased")
     if args.zarr is None:
-        _PRELOADED = (args.vcf, vcf["calldata/GT"], vcf["samples"])
+        _PRELOADED = (args.vcf, vcf["calldata/GT"], vcf["samples"], vcf)
 
 
 # ------------------------------------------------------------------ ingest (locator.py:187-308)
 def load_genotypes():
     """(variants, samples, 2) int8 calls and the sample IDs from whichever of --zarr / --vcf / --matrix was given
-    (locator.py:187-228); the readers live in genotypes.py (no scikit-allel / zarr dependency)."""
+    (locator.py:187-228); the readers live in genotypes.py (no scikit-allel / zarr dependency).  With --keep_model the
+    identity of every input variant is read too (_VARIANTS)."""
+    global _VARIANTS
+    _VARIANTS = None
     if args.zarr is not None:
         print("reading zarr")
         callset = G.open_group(args.zarr, mode="r")
@@ -231,18 +245,61 @@ def load_genotypes():
             za.read_into(gt, 0, za.shape[0], threads=G.HOST_THREADS)
         else:
             gt = np.asarray(za[:], dtype=np.int8)
+        if _keep_model():
+            _VARIANTS = _variant_table()
         return gt, np.asarray(callset["samples"][:])
     if args.vcf is not None:
         global _PRELOADED
         loaded, _PRELOADED = _PRELOADED, None
         if loaded is not None and loaded[0] == args.vcf:
+            if _keep_model():
+                _VARIANTS = _site_columns(loaded[3])
             return loaded[1], loaded[2]
         print("reading VCF")
-        vcf = G.read_vcf(args.vcf)
+        vcf = G.read_vcf(args.vcf, sites=_keep_model())
+        if _keep_model():
+            _VARIANTS = _site_columns(vcf)
         return vcf["calldata/GT"], vcf["samples"]
     if args.matrix is not None:
+        if _keep_model():
+            _VARIANTS = _variant_table()
         return G.read_matrix(args.matrix)
     raise SystemExit("one of --zarr, --vcf or --matrix is required")
+
+
+_VARIANTS = None       # --keep_model: {chrom, pos, ref, alt} of every input variant (load_genotypes / _variant_table)
+
+
+def _site_columns(d):
+    """read_vcf(sites=True) / zarr_sites dict -> {chrom, pos, ref, alt}: ALT[0] of each variant."""
+    alt = np.asarray(d["variants/ALT"], dtype=object)
+    return {"chrom": np.asarray(d["variants/CHROM"], dtype=object).astype(str),
+            "pos": np.asarray(d["variants/POS"], dtype=np.int64),
+            "ref": np.asarray(d["variants/REF"], dtype=object).astype(str),
+            "alt": (alt[:, 0] if alt.ndim == 2 else alt).astype(str)}
+
+
+def _variant_table():
+    """--keep_model: the identity of every variant of the run's genotype source.  A --matrix column is its header name
+    (POS -1, no alleles); a zarr store must hold variants/CHROM, REF and ALT."""
+    if args.zarr is not None:
+        try:
+            return _site_columns(G.zarr_sites(G.open_group(args.zarr, mode="r")))
+        except KeyError as e:
+            raise SystemExit(f"--keep_model: {args.zarr} has no {e.args[0]}: the model file records CHROM, POS, REF and ALT "
+                             "of every site") from None
+    if args.vcf is not None:
+        return _site_columns(G.read_vcf(args.vcf, sites=True))
+    names = G.matrix_sites(args.matrix).astype(str)
+    empty = np.full(len(names), "", dtype=str)
+    return {"chrom": names, "pos": np.full(len(names), -1, np.int64), "ref": empty, "alt": empty}
+
+
+def _model_sites(variants, idx, af):
+    """The site table of a model file: the input variant of every column (idx, in column order) and its allele-1 frequency."""
+    idx = np.asarray(idx, dtype=np.int64)
+    return {"chrom": variants["chrom"][idx], "pos": variants["pos"][idx], "ref": variants["ref"][idx],
+            "alt": variants["alt"][idx], "af": np.asarray(af, dtype=np.float64)}
 
 
 def sort_samples(samples, genotypes):
@@ -269,13 +326,13 @@ def replace_md(genotypes):
     return G.replace_md(genotypes)
 
 
-def filter_snps(genotypes):
+def filter_snps(genotypes, sites=False):
     """--phased: the same filters on the haplotype view (V, 2N, 1): the same sites pass, the matrix holds 0/1 per
-    haplotype row."""
+    haplotype row.  sites=True: (matrix, input variant index of every row) - no other draw than without it."""
     if _phased():
         genotypes = G.haplotypes(genotypes)
     return G.filter_snps(genotypes, min_mac=args.min_mac, max_snps=args.max_SNPs,
-                         impute_missing=args.impute_missing)
+                         impute_missing=args.impute_missing, sites=sites)
 
 
 def normalize_locs(locs):
@@ -421,14 +478,46 @@ def load_callbacks(boot):
 WEIGHT_KEYS = ("gamma", "beta", "moving_mean", "moving_variance")
 
 
-def save_weights(path, w):
-    """--keep_weights artefact: NumPy archive in Keras tensor orientation (the reference keeps a Keras HDF5 file,
-    locator.py:332-348; h5py is not available here)."""
+def _weight_arrays(w):
     flat = {"gamma": w["gamma"], "beta": w["beta"], "moving_mean": w["mov_mean"], "moving_variance": w["mov_var"]}
     for i, (k, b) in enumerate(zip(w["W"], w["b"])):
         flat[f"dense_{i}_kernel"], flat[f"dense_{i}_bias"] = k, b
     flat["n_snps"], flat["width"], flat["nlayers"] = (np.int64(w["W"][0].shape[0]), np.int64(w["W"][0].shape[1]),
                                                       np.int64(len(w["W"]) - 2))
+    return flat
+
+
+def save_weights(path, w):
+    """--keep_weights artefact: NumPy archive in Keras tensor orientation (the reference keeps a Keras HDF5 file,
+    locator.py:332-348; h5py is not available here)."""
+    flat = _weight_arrays(w)
+    _write_atomic(path, lambda fh: np.savez(fh, **flat), mode="wb")
+
+
+MODEL_FORMAT_VERSION = 1
+
+
+def _model_path(boot):
+    return _weights_path(boot)[:-len(".weights.npz")] + ".model.npz"
+
+
+def save_model(path, w, meta):
+    """--keep_model artefact: every array of save_weights under the same names (read_weights / --load_weights take the
+    file as it is), the site table - CHROM, POS, REF, ALT[0] and allele-1 frequency of the input variant of every column,
+    in column order - the coordinate normalisation [meanlong, sdlong, meanlat, sdlat], ploidy, phased, format_version and
+    the run's params.json text.  Strings are fixed-width unicode: np.load(allow_pickle=False) reads the file."""
+    flat = _weight_arrays(w)
+    K = int(w["W"][0].shape[0])
+    sites = {"site_chrom": np.asarray(meta["chrom"]).astype(str), "site_pos": np.asarray(meta["pos"], dtype=np.int64),
+             "site_ref": np.asarray(meta["ref"]).astype(str), "site_alt": np.asarray(meta["alt"]).astype(str),
+             "site_af": np.asarray(meta["af"], dtype=np.float64)}
+    for k, v in sites.items():
+        if v.shape != (K,):
+            raise ValueError(f"--keep_model: {k} holds {v.shape} entries for a model of {K} SNPs")
+    flat.update(sites)
+    flat.update(locs_norm=np.asarray(meta["locs_norm"], dtype=np.float64), ploidy=np.int64(meta["ploidy"]),
+                phased=np.bool_(meta["phased"]), format_version=np.int64(MODEL_FORMAT_VERSION),
+                params_json=np.array(str(meta["params_json"])))
     _write_atomic(path, lambda fh: np.savez(fh, **flat), mode="wb")
 
 
@@ -497,6 +586,13 @@ def train_network(model, traingen, testgen, trainlocs, testlocs, callbacks, boot
         w = model.weights_dict()                     # device read-back: under the lock
         with _host_io():
             save_weights(checkpointer["filepath"], w)
+    if _keep_model():
+        meta = getattr(_TLS, "model_meta", None)
+        if meta is None:
+            raise RuntimeError("--keep_model: this fit has no site table")
+        w = model.weights_dict()
+        with _host_io():
+            save_model(_model_path(boot), w, meta)
     print("run time " + str((time.time() - start) / 60) + " minutes")
     return history, model
 
@@ -717,7 +813,13 @@ def _fit_unit_body(unit, device="cuda:0"):
             gt_dev = gt_dev.view(shape[0], shape[1] * shape[2], 1)        # [variants][2N haplotypes][1]
         train, test, pred = unit["train"], unit["test"], unit["pred"]
         order = np.concatenate([np.asarray(train), np.asarray(test), np.asarray(pred)]).astype(np.int32)
-        X, K = filter_snps_device(gt_dev, order, args.min_mac)
+        if _keep_model(args):
+            X, K, keep = filter_snps_device(gt_dev, order, args.min_mac, return_keep=True)
+            idx = np.flatnonzero(keep)
+            host = pin.numpy()[:nbytes].view(np.int8).reshape(shape)
+            unit["model_sites"] = _model_sites(unit["variants"], idx, G.site_af(host, idx))
+        else:
+            X, K = filter_snps_device(gt_dev, order, args.min_mac)
         torch.cuda.current_stream().synchronize()
         _pin_give(pin)
         del gt_dev
@@ -748,6 +850,7 @@ def _fit_unit_body(unit, device="cuda:0"):
     # every file of this unit hangs off the unit's own stem (for a window: {out}_{start}-{end}; the reference swaps
     # args.out only after training, so its --keep_weights file is overwritten by every window)
     _TLS.out = unit["out"]              # thread-local: another unit may be fitting on another thread / stream of this process
+    _TLS.model_meta = _unit_model_meta(unit)
     try:
         callbacks = load_callbacks(unit["boot"])
         t1 = time.time()
@@ -760,8 +863,21 @@ def _fit_unit_body(unit, device="cuda:0"):
         phases["predict"] = time.time() - t1
     finally:
         _TLS.out = None
+        _TLS.model_meta = None
     return {"name": unit["name"], "history": history.history, "dists": dists, "seconds": time.time() - t_unit,
             "phases": phases, "epochs": len(history.history.get("loss", []))}
+
+
+def _unit_model_meta(unit):
+    """--keep_model: what save_model writes besides the weights, for this unit's fit - its site table (a bootstrap
+    replicate's columns are the base sites in site_order, repeats included), normalisation, ploidy, phase, parameters."""
+    if not _keep_model(unit["args"]):
+        return None
+    sites = unit["model_sites"]
+    if unit.get("site_order") is not None:
+        sites = {k: v[np.asarray(unit["site_order"], dtype=np.int64)] for k, v in sites.items()}
+    return dict(sites, locs_norm=[unit["meanlong"], unit["sdlong"], unit["meanlat"], unit["sdlat"]],
+                ploidy=int(unit.get("ploidy", 2)), phased=_phased(unit["args"]), params_json=unit["params_json"])
 
 
 _PIN_POOL = []          # per worker process: pinned staging buffers for window slices (torch uint8 tensors), reused
@@ -846,6 +962,7 @@ def _window_units(samples, lazy=None):
         lazy = not args.impute_missing and args.max_SNPs is None
     units = []
     ids = row_ids(samples)
+    variants = _variant_table() if _keep_model() else None
     for n, (i, size, a, b) in enumerate(_window_bounds()):
         print(f"\nProcessing window {i}-{i + size}")
         print(f"SNPs {a}-{b}")
@@ -853,6 +970,9 @@ def _window_units(samples, lazy=None):
                     samples=ids)
         if _phased():
             unit["phased"] = True           # rows are haplotypes: the window's calls are viewed as (V, 2N, 1)
+        if variants is not None:            # --keep_model: the identities of the window's variants gt[a:b]
+            unit.update(variants={k: v[a:b] for k, v in variants.items()}, params_json=_PARAMS_TEXT,
+                        ploidy=int(G.open_group(args.zarr, mode="r")["calldata/GT"].shape[2]))
         if lazy:
             class _Shape:
                 shape = (b - a, len(samples), 2)
@@ -876,17 +996,21 @@ def _load_window(unit, draw_split=False, individuals=None):
     a, b = unit["window"]
     gt = G.open_group(unit["zarr"], mode="r")["calldata/GT"]
     genotypes = np.asarray(gt[a:b, :, :], dtype=np.int8)
+    keep_model = "variants" in unit
     if draw_split:                                   # eager path: reference order sort -> normalise -> filter -> split
         meanlong, sdlong, meanlat, sdlat, locs = row_locs(unit["samples"] if individuals is None else individuals,
                                                           genotypes)
-        ac = filter_snps(genotypes)
+        ac = filter_snps(genotypes, sites=keep_model)
         train, test, pred = split_rows(locs, args.train_split)
         unit.update(sdlong=sdlong, meanlong=meanlong, sdlat=sdlat, meanlat=meanlat)
     else:
-        if unit.get("phased"):
-            genotypes = G.haplotypes(genotypes)
-        ac = G.filter_snps(genotypes, min_mac=unit["args"].min_mac if "args" in unit else args.min_mac, verbose=False)
+        calls = G.haplotypes(genotypes) if unit.get("phased") else genotypes
+        ac = G.filter_snps(calls, min_mac=unit["args"].min_mac if "args" in unit else args.min_mac, verbose=False,
+                           sites=keep_model)
         train, test, pred, locs = unit["train"], unit["test"], unit["pred"], unit["locs"]
+    if keep_model:
+        ac, idx = ac
+        unit["model_sites"] = _model_sites(unit["variants"], idx, G.site_af(genotypes, idx))
     unit.update(traingen=G.rows_transposed(ac, train), testgen=G.rows_transposed(ac, test),
                 predgen=(G.rows_transposed(ac, pred) if len(pred) else np.zeros((0, ac.shape[0]), ac.dtype)),
                 trainlocs=locs[train], testlocs=locs[test], pred=pred)
@@ -909,6 +1033,9 @@ def _bootstrap_units(n_sites):
     return units
 
 
+_BASE_SITES = None     # --keep_model: the site table of the run's filtered matrix (single run, --bootstrap, --jacknife)
+
+
 def _prologue(force_full=False):
     """locator.py:507-516.  Returns (samples, state) where state is None in the windows fast path or the
     tuple (meanlong, sdlong, meanlat, sdlat, ac, train, test, traingen, testgen, trainlocs, testlocs, pred, predgen).
@@ -928,9 +1055,16 @@ def _prologue(force_full=False):
         meanlong, sdlong, meanlat, sdlat, locs = normalize_locs(locs)
         split_indices(locs, args.train_split)        # --phased: the same draw (over individuals)
         return samples, None
+    global _BASE_SITES
     genotypes, samples = load_genotypes()
     meanlong, sdlong, meanlat, sdlat, locs = row_locs(samples, genotypes)
-    ac = filter_snps(genotypes)
+    _BASE_SITES = None
+    if _keep_model():
+        ac, idx = filter_snps(genotypes, sites=True)
+        _BASE_SITES = _model_sites(_VARIANTS, idx, G.site_af(genotypes, idx))
+        _BASE_SITES["ploidy"] = int(np.shape(genotypes)[2])
+    else:
+        ac = filter_snps(genotypes)
     train, test, traingen, testgen, trainlocs, testlocs, pred, predgen = split_train_test(ac, locs)
     return samples, (meanlong, sdlong, meanlat, sdlat, ac, train, test, traingen, testgen, trainlocs, testlocs,
                      pred, predgen)
@@ -998,6 +1132,15 @@ def main(argv=None):
             pool.close()
 
 
+def _model_fields():
+    """--keep_model: the unit fields _unit_model_meta reads (nothing without the flag)."""
+    if not _keep_model():
+        return {}
+    sites = dict(_BASE_SITES)
+    ploidy = sites.pop("ploidy")
+    return {"model_sites": sites, "ploidy": ploidy, "params_json": _PARAMS_TEXT}
+
+
 def _main_body(pool, t_program):
     samples, state = _prologue()
     if state is not None:
@@ -1021,14 +1164,15 @@ def _main_body(pool, t_program):
     elif not args.bootstrap and not args.jacknife:
         unit = dict(name="single", replicate=0, boot=0, out=args.out, traingen=traingen, testgen=testgen,
                     predgen=predgen, trainlocs=trainlocs, testlocs=testlocs, pred=pred, samples=row_ids(samples),
-                    sdlong=sdlong, meanlong=meanlong, sdlat=sdlat, meanlat=meanlat, args=args)
+                    sdlong=sdlong, meanlong=meanlong, sdlat=sdlat, meanlat=meanlat, args=args, **_model_fields())
         r = _fit_unit(unit, reraise=True)
         plot_history(_H(r["history"]), r["dists"])
     elif args.bootstrap:
         units = _bootstrap_units(traingen.shape[1])
         shared = dict(traingen=np.ascontiguousarray(traingen), testgen=np.ascontiguousarray(testgen),
                       predgen=np.ascontiguousarray(predgen), trainlocs=trainlocs, testlocs=testlocs, pred=pred,
-                      samples=row_ids(samples), sdlong=sdlong, meanlong=meanlong, sdlat=sdlat, meanlat=meanlat, out=args.out)
+                      samples=row_ids(samples), sdlong=sdlong, meanlong=meanlong, sdlat=sdlat, meanlat=meanlat, out=args.out,
+                      **_model_fields())
         results = pool.run(units, shared)
         _print_replicate_summary(pool, results, t_program)
         failed = sum("error" in r for r in results)
@@ -1070,8 +1214,13 @@ def _jacknife(ac, traingen, testgen, trainlocs, testlocs, predgen, pred, samples
     perturbed copies form ONE matrix of nboots x n_pred rows that goes up once and through one many-row predict (the
     first layer as a large-M GEMM against a weight image converted once)."""
     t_fit = time.time()
-    history, model = train_network(load_network(traingen, args.dropout_prop), traingen, testgen, trainlocs, testlocs,
-                                   load_callbacks("FULL"), "FULL")
+    _TLS.model_meta = _unit_model_meta(dict(_model_fields(), args=args, meanlong=meanlong, sdlong=sdlong, meanlat=meanlat,
+                                            sdlat=sdlat))
+    try:
+        history, model = train_network(load_network(traingen, args.dropout_prop), traingen, testgen, trainlocs, testlocs,
+                                       load_callbacks("FULL"), "FULL")
+    finally:
+        _TLS.model_meta = None
     plot_history(history, predict_locs(model, predgen, sdlong, meanlong, sdlat, meanlat, testlocs, pred, samples,
                                        testgen, history, "FULL"))
     print("run time " + str((time.time() - t_fit) / 60) + " minutes")

@@ -498,11 +498,12 @@ def gather_columns(X, site_order, K):
     return out
 
 
-def filter_snps_device(gt, sample_order, min_mac=2):
+def filter_snps_device(gt, sample_order, min_mac=2, return_keep=False):
     """filter_snps (locator.py:265-273, no --impute_missing / --max_SNPs) and the split's `ac[:, rows].T` (:295-308) on the
     device.  gt: int8 device tensor [n_variants][n_samples][ploidy] (the window's zarr slice, uploaded as it is);
     sample_order: the rows wanted, in output order (train | validation | prediction).  Returns (X uint8 [len(order)][Kp],
-    K).  One host synchronisation: the SNP count decides the allocation."""
+    K) - and with return_keep the host copy of the keep flags (which variant each column came from: --keep_model).  One host
+    synchronisation: the SNP count decides the allocation."""
     lib = _lib.load()
     assert gt.dtype == torch.int8 and gt.is_cuda and gt.is_contiguous() and gt.dim() == 3
     V, N, P = (int(v) for v in gt.shape)
@@ -519,4 +520,6 @@ def filter_snps_device(gt, sample_order, min_mac=2):
     if K > 0:
         _lib.check(lib.loc_filter_snps_rows(_ptr(gt), V, N, P, _ptr(keep), _ptr(pos), _ptr(order), len(order), _ptr(X),
                                             X.stride(0), _stream()), "loc_filter_snps_rows")
+    if return_keep:
+        return X, K, keep.cpu().numpy()
     return X, K
