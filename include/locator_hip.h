@@ -249,6 +249,18 @@ int loc_gather_columns(const uint8_t* src, int64_t src_pitch, const int32_t* sit
  * One workgroup per sample, float64, fixed summation order (launch-independent results). */
 int loc_kde_peak_batch(const double* xy, const int64_t* offsets, int n_samples, double bandwidth, int32_t* peak_index,
                        double* out, void* stream);
+/* Density grids of the plot command (locator_amd/plot.py), the per-sample maps drawn after --windows / --bootstrap.
+ * Panel s owns the points pts[pt_off[s] .. pt_off[s+1]) ([lat, lon] pairs, radians), the grid latitudes
+ * lat_axis[lat_off[s] .. lat_off[s+1]) (ny values, radians) and longitudes lon_axis[lon_off[s] .. lon_off[s+1]) (nx), and
+ * writes z[z_off[s] + iy * nx + ix] (z_off[s+1] - z_off[s] == ny * nx) =
+ *   sum_i exp(-d_i^2 / (2 h^2)) / (n * 2 pi h^2),  d_i = haversine distance (radians) from the grid point to point i
+ * = exp(sklearn KernelDensity(kernel='gaussian', metric='haversine', bandwidth=h).score_samples(grid)).
+ * float64; every grid point sums its points in index order, so values do not depend on the launch or the other panels.
+ * A panel with no points or with a non-finite point is NaN over its whole grid.  The offsets are read back to check the
+ * sizes first (the call synchronises the stream); bad sizes or h <= 0 return nonzero and launch nothing. */
+int loc_kde_grid_batch(const double* pts, const int64_t* pt_off, const double* lat_axis, const int64_t* lat_off,
+                       const double* lon_axis, const int64_t* lon_off, int n_panels, double bandwidth, double* z,
+                       const int64_t* z_off, void* stream);
 /* out[0] = max(out[0], largest byte of X[0..n_rows)[0..K)) (uint32, zero it first): which number formats can carry the
  * genotypes exactly (int8 needs <= 127). */
 int loc_genotype_max(const uint8_t* X, int64_t x_pitch, int n_rows, int K, uint32_t* out, void* stream);

@@ -494,6 +494,13 @@ class ZarrGroup:
             return ZarrGroup(p)
         raise KeyError(key)
 
+    def __iter__(self):
+        """Member names (arrays and sub-groups: the sub-directories, as __getitem__ opens them) in sorted order, as
+        `zarr` lists a group's keys."""
+        for name in sorted(os.listdir(self.path)):
+            if not name.startswith(".") and os.path.isdir(os.path.join(self.path, name)):
+                yield name
+
 
 def open_group(path, mode="r"):
     return ZarrGroup(path)
