@@ -579,6 +579,24 @@ int loc_query_rows(const int8_t* gt, int64_t n_variants, int n_samples, int ploi
                    const int8_t* col_allele, int K, const int32_t* sample_order, int n_out, uint8_t* X, int64_t x_pitch,
                    void* stream);
 
+/* ---- per-SNP attribution of a kept model (python -m locator_amd.explain; DESIGN.md §8, the explain command) ----
+ * loc_explain_stack_grad: a1 = layer 1's ELU output [n][Hp] (loc_l1_forward_rows / loc_l1_forward, exact form); wh / bh / wa / wb
+ * as the parameter layout holds them.  Runs the hidden stack forward keeping every activation (acts: (L-1)*n*Hp floats, NULL
+ * when L == 1), then back-propagates the two map-unit seeds (sd_x * Wa Wb[:,0], sd_y * Wa Wb[:,1]) with elu' taken from the
+ * stored activations (g: 2*n*Hp floats of scratch, NULL when L == 1).  delta1[(2 i + j)][h] = d(x^, y^)_j / d z1[i][h].
+ * loc_explain_sites: D[(i, j)][s] = sum_h delta1[(i, j)][h] U[s][h] (U = [Ks][Hp] fp32: the first layer scaled by the
+ * BatchNorm scale and summed over the model columns of site s) on the fp32 matrix pipe; per site the sums over the rows of
+ * each split of |A_x|, |A_y|, sqrt(A_x^2 + A_y^2) and J_x^2 + J_y^2, A = D (Xs[i][s] - mov_mean[s]) (Xs: uint8 [n][xs_pitch],
+ * one column per site) -> partial[split][4][Ks] fp64.  splits from loc_explain_splits (workgroups to fill compute_units).
+ * loc_explain_reduce: out[4][Ks] fp64 = the splits summed in order, divided by n (square root of the fourth: rms_grad).
+ * No atomics: bit-identical from run to run.  n <= 2^29; every offset is 64-bit. */
+int loc_explain_stack_grad(const float* a1, int n, int Hp, int L, const float* wh, const float* bh, const float* wa,
+                           const float* wb, float sd_x, float sd_y, float* acts, float* g, float* delta1, void* stream);
+int loc_explain_splits(int n, int Ks, int compute_units);
+int loc_explain_sites(const float* delta1, int n, const float* U, int Ks, int Hp, const uint8_t* Xs, int64_t xs_pitch,
+                      const float* mov_mean, int splits, double* partial, void* stream);
+int loc_explain_reduce(const double* partial, int splits, int Ks, int n, double* out, void* stream);
+
 /* ---- the three callbacks of a fit, on the device (locator.py:330-362) ----
  * State of ModelCheckpoint(best only) -> EarlyStopping -> ReduceLROnPlateau, all on val_loss, strict '<', min_delta 0.
  * The host fills it once (bests = +inf, waits 0, lr = the fit's starting rate, epoch 0, stopped 0, stop_epoch / best_epoch

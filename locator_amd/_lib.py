@@ -154,6 +154,11 @@ SIGNATURES = {
     "loc_filter_snps_flags": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "loc_filter_snps_rows": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int64, vp]),
     "loc_query_rows": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int64, vp]),
+    "loc_explain_stack_grad": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp,
+                                         vp]),
+    "loc_explain_splits": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "loc_explain_sites": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int, vp, vp]),
+    "loc_explain_reduce": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "loc_epoch_callbacks": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
     "loc_snapshot_if": (C.c_int, [vp, vp, vp, C.c_int64, vp]),
     "loc_event_create": (C.c_int, [C.POINTER(vp)]),
