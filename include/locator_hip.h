@@ -290,6 +290,20 @@ int loc_bn_epoch_stats_only(const uint8_t* X, int64_t x_pitch, const int32_t* ro
                             int K, int Kp, float* stats_ep, void* stream);
 int loc_bn_epoch_finish(int n_steps, int K, int Kp, const float* gamma, const float* beta, float* mov_mean, float* mov_var,
                         const float* stats_ep, float* bn4, void* stream);
+/* --dosage: X holds expected alt-allele dosages d in fixed point, q = rint(fp32(d) * LOC_DOSAGE_UNIT)
+ * clamped to 0..2 * LOC_DOSAGE_UNIT (126: the int8 GEMM's x_max <= 127 still holds).  The model is the one on d = q / unit:
+ * the two entry points below take the unit as a trailing argument and write the COMPENSATED variance
+ * var' = var_q + loc_bn_var_add(unit), loc_bn_var_add(u) = (u^2 - 1) * BN_EPS in fp32, so that every reader's
+ * 1 / sqrt(var' + BN_EPS) is rstd_d / unit and scale / shift of q give exactly BN(d).  mov_mean / mov_var then live in the same
+ * units (mean_q = unit * mean_d, var' = unit^2 * var_d + var_add); a fresh net starts at mov_var = unit^2 + var_add, and
+ * weights convert back to dosage units where they leave the device (locator_amd/net.py).  unit = 1 runs the GT kernels. */
+#define LOC_DOSAGE_UNIT 63
+float loc_bn_var_add(int unit);
+int loc_bn_epoch_stats_unit(const uint8_t* X, int64_t x_pitch, const int32_t* rows_all, int batch, int n_last, int n_steps,
+                            int K, int Kp, const float* gamma, const float* beta, float* mov_mean, float* mov_var,
+                            float* stats_ep, float* bn4, int unit, void* stream);
+int loc_bn_epoch_stats_only_unit(const uint8_t* X, int64_t x_pitch, const int32_t* rows_all, int batch, int n_last,
+                                 int n_steps, int K, int Kp, float* stats_ep, int unit, void* stream);
 /* Inference: scale/shift from the moving statistics. */
 int loc_bn_infer_scale_shift(int K, int Kp, const float* gamma, const float* beta, const float* mov_mean,
                              const float* mov_var, float* out4, void* stream);
@@ -568,6 +582,15 @@ int loc_filter_snps_flags(const int8_t* gt, int64_t n_variants, int n_samples, i
                           int32_t* pos, int32_t* n_kept, void* stream);
 int loc_filter_snps_rows(const int8_t* gt, int64_t n_variants, int n_samples, int ploidy, const uint8_t* keep,
                          const int32_t* pos, const int32_t* sample_order, int n_out, uint8_t* X, int64_t x_pitch, void* stream);
+/* --dosage forms for a window's dosages ds float32 [n_variants][n_samples] (NaN = missing; 64-bit offsets throughout).
+ * q = rint(fp32(d) * LOC_DOSAGE_UNIT) clamped to 0..2 * LOC_DOSAGE_UNIT.  loc_dosage_flags: keep[v] = 1 iff over the called
+ * samples S = sum(q) >= LOC_DOSAGE_UNIT * min_mac, S > 0 and S < 2 * LOC_DOSAGE_UNIT * n_called; pos / n_kept as above.
+ * loc_dosage_rows: X[r][pos[v]] = q of sample sample_order[r] at kept variant v (missing -> 0).  Bit-identical to
+ * genotypes.dosage_q + genotypes.filter_dosage + the NumPy transposes. */
+int loc_dosage_flags(const float* ds, int64_t n_variants, int n_samples, int min_mac, uint8_t* keep, int32_t* pos,
+                     int32_t* n_kept, void* stream);
+int loc_dosage_rows(const float* ds, int64_t n_variants, int n_samples, const uint8_t* keep, const int32_t* pos,
+                    const int32_t* sample_order, int n_out, uint8_t* X, int64_t x_pitch, void* stream);
 
 /* ---- a kept model on a new genotype file (python -m locator_amd.predict; locator_amd/query.py matches the sites) ----
  * gt: the query's calls int8 [n_variants][n_samples][ploidy] (negative = missing); col_variant[k]: the query variant of model

@@ -77,6 +77,11 @@ SIGNATURES = {
     "loc_w1_swizzle": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]),
     "loc_w1_unswizzle": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]),
     "loc_bn_batch_stats": (C.c_int, [vp, C.c_int64, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "loc_bn_var_add": (C.c_float, [C.c_int]),
+    "loc_bn_epoch_stats_unit": (C.c_int, [vp, C.c_int64, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp,
+                                          vp, vp, C.c_int, vp]),
+    "loc_bn_epoch_stats_only_unit": (C.c_int, [vp, C.c_int64, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
+                                               vp]),
     "loc_bn_infer_scale_shift": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
     "loc_l1_forward": (C.c_int, [vp, C.c_int64, vp, C.c_int, C.POINTER(Dims), vp, vp, vp, vp, C.c_int, vp, vp, vp,
                                  C.c_float, vp]),
@@ -153,6 +158,8 @@ SIGNATURES = {
     "loc_predict_image_mode": (C.c_int, [C.POINTER(Net), C.c_int]),
     "loc_filter_snps_flags": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "loc_filter_snps_rows": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int64, vp]),
+    "loc_dosage_flags": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "loc_dosage_rows": (C.c_int, [vp, C.c_int64, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int64, vp]),
     "loc_query_rows": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int64, vp]),
     "loc_explain_stack_grad": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp,
                                          vp]),

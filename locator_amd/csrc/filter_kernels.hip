@@ -142,3 +142,106 @@ extern "C" int loc_filter_snps_rows(const int8_t* gt, int64_t n_variants, int n_
     LOC_CHECK_LAUNCH();
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// --dosage: the same two passes over a window's expected alt-allele dosages, float32 [variants][samples] (calldata/DS; NaN =
+// missing), for the fixed-point genotype matrix of DESIGN.md section 3: q = rint(fp32(d) * 63) clamped to 0..126
+// (genotypes.dosage_q is the host form).  A single product and a rounding - nothing for fp32 contraction to fuse - so the
+// device and the NumPy form agree bit for bit.  Filter (genotypes.filter_dosage): over the called samples,
+// S = sum(q) >= 63 * min_mac, S > 0 and S < 126 * n_called (not monomorphic).  All offsets into the slice are 64-bit:
+// a 720k-variant window of 765 samples is 2.2 GB.
+__device__ __forceinline__ int dosage_q_dev(float d) {
+    if (d != d) return -1;                           // NaN: missing
+    const float f = fminf(fmaxf(rintf(d * (float)LOC_DOSAGE_UNIT), 0.f), (float)(2 * LOC_DOSAGE_UNIT));
+    return (int)f;
+}
+
+// One wave per variant, lanes over the samples (64 consecutive floats per load instruction).
+__global__ __launch_bounds__(256) void dosage_flags_kernel(const float* __restrict__ ds, int64_t n_variants, int n_samples,
+                                                           int min_mac, uint8_t* __restrict__ keep) {
+    const int lane = threadIdx.x & 63;
+    const int64_t v = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (v >= n_variants) return;
+    const float* row = ds + v * (int64_t)n_samples;
+    int64_t s = 0;
+    int called = 0;
+    for (int i = lane; i < n_samples; i += 64) {
+        const int q = dosage_q_dev(row[i]);
+        if (q >= 0) {
+            s += q;
+            called += 1;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o);
+        called += __shfl_xor(called, o);
+    }
+    if (lane == 0)
+        keep[v] = (s >= (int64_t)LOC_DOSAGE_UNIT * min_mac && s > 0 && s < (int64_t)(2 * LOC_DOSAGE_UNIT) * called) ? 1 : 0;
+}
+
+// snp_rows_kernel with q in place of the allele-1 count (missing -> 0): the tile of FT variants x FS samples in LDS, then
+// rows written as contiguous runs of kept positions.
+__global__ __launch_bounds__(256) void dosage_rows_kernel(const float* __restrict__ ds, int64_t n_variants, int n_samples,
+                                                          const uint8_t* __restrict__ keep, const int32_t* __restrict__ pos,
+                                                          const int32_t* __restrict__ sample_order, int n_out,
+                                                          uint8_t* __restrict__ X, int64_t x_pitch) {
+    __shared__ uint8_t tile[FT][FS + FPAD];
+    __shared__ int32_t slot[FT];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int64_t v0 = (int64_t)blockIdx.x * FT;
+    const int nv = n_variants - v0 < FT ? (int)(n_variants - v0) : FT;
+    const int32_t pos0 = pos[v0];
+    if (t < FT) slot[t] = (t < nv && keep[v0 + t]) ? pos[v0 + t] - pos0 : -1;
+    __syncthreads();
+    const int cnt = pos[v0 + nv - 1] - pos0 + keep[v0 + nv - 1];
+    if (cnt == 0) return;
+    for (int s0 = 0; s0 < n_samples; s0 += FS) {
+        const int ns = n_samples - s0 < FS ? n_samples - s0 : FS;
+        __syncthreads();
+        for (int j = 0; j < nv; ++j) {
+            const int sl = slot[j];
+            if (sl < 0) continue;
+            const float* row = ds + (v0 + j) * (int64_t)n_samples + s0;
+            for (int s = t; s < ns; s += 256) {
+                const int q = dosage_q_dev(row[s]);
+                tile[sl][s] = (uint8_t)(q < 0 ? 0 : q);
+            }
+        }
+        __syncthreads();
+        for (int r = w; r < n_out; r += 4) {
+            const int s = sample_order[r] - s0;
+            if (s < 0 || s >= ns) continue;
+            if (lane < cnt) X[(int64_t)r * x_pitch + pos0 + lane] = tile[lane][s];
+        }
+    }
+}
+
+extern "C" int loc_dosage_flags(const float* ds, int64_t n_variants, int n_samples, int min_mac, uint8_t* keep, int32_t* pos,
+                                int32_t* n_kept, void* stream) {
+    if (n_variants < 1 || n_samples < 1 || n_variants > ((int64_t)1 << 31) - 1024) {
+        loc_set_error("loc_dosage_flags: n_variants=%lld n_samples=%d", (long long)n_variants, n_samples);
+        return -1;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(dosage_flags_kernel, dim3((unsigned)((n_variants + 3) / 4)), dim3(256), 0, st, ds, n_variants, n_samples,
+                       min_mac, keep);
+    LOC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(snp_scan_kernel, dim3(1), dim3(1024), 0, st, keep, n_variants, pos, n_kept);
+    LOC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int loc_dosage_rows(const float* ds, int64_t n_variants, int n_samples, const uint8_t* keep, const int32_t* pos,
+                               const int32_t* sample_order, int n_out, uint8_t* X, int64_t x_pitch, void* stream) {
+    if (n_variants < 1 || n_samples < 1 || n_out < 0 || n_variants > ((int64_t)1 << 31) - 1024) {
+        loc_set_error("loc_dosage_rows: n_variants=%lld n_samples=%d n_out=%d", (long long)n_variants, n_samples, n_out);
+        return -1;
+    }
+    if (n_out == 0) return 0;
+    hipLaunchKernelGGL(dosage_rows_kernel, dim3((unsigned)((n_variants + FT - 1) / FT)), dim3(256), 0, (hipStream_t)stream, ds,
+                       n_variants, n_samples, keep, pos, sample_order, n_out, X, x_pitch);
+    LOC_CHECK_LAUNCH();
+    return 0;
+}

@@ -39,8 +39,9 @@ __global__ __launch_bounds__(128) void bn_batch_stats_kernel(
         const int k = k0 + c;
         if (k < K) {
             float mean = (float)s[c] / (float)n_b;
-            // biased variance, exact integer numerator: (n*sum(x^2) - sum(x)^2) / n^2
-            float var = (float)(n_b * ss[c] - s[c] * s[c]) / (float)(n_b * n_b);
+            // biased variance, exact integer numerator: (n*sum(x^2) - sum(x)^2) / n^2; 64-bit as in the epoch kernel below
+            // (the value is the same integer wherever 32 bits did not overflow)
+            float var = (float)((int64_t)n_b * ss[c] - (int64_t)s[c] * s[c]) / (float)(n_b * n_b);
             float rstd = 1.0f / sqrtf(var + BN_EPS);
             float scale = gamma[k] * rstd;
             o_sc[c] = scale;
@@ -61,11 +62,15 @@ __global__ __launch_bounds__(128) void bn_batch_stats_kernel(
 // BN batch statistics for EVERY minibatch of an epoch in one launch: they depend only on the genotype
 // matrix and the epoch's permutation, not on any weight.  Grid (SNP quads, steps).
 // stats_ep[step] = [mean | biased var] (2*Kp floats).
+// UNIT (--dosage, include/locator_hip.h LOC_DOSAGE_UNIT): X holds q = unit * d; the variance written is
+// var_q + var_add, var_add = (unit^2 - 1) * BN_EPS, so that every reader's 1 / sqrt(var + BN_EPS) is rstd_d / unit and
+// the BatchNorm of q is exactly that of d.  The GT instantiation (UNIT = false) ignores var_add.
 // ---------------------------------------------------------------------------------------------
+template <bool UNIT>
 __global__ __launch_bounds__(128) void bn_epoch_stats_kernel(const uint8_t* __restrict__ X, int64_t pitch,
                                                              const int32_t* __restrict__ rows_all, int batch,
                                                              int n_last, int n_steps, int K, int Kp,
-                                                             float* __restrict__ stats_ep) {
+                                                             float* __restrict__ stats_ep, float var_add) {
     const int k0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const int step = blockIdx.y;
     if (k0 >= Kp) return;
@@ -89,6 +94,7 @@ __global__ __launch_bounds__(128) void bn_epoch_stats_kernel(const uint8_t* __re
             mu[c] = (float)s[c] / (float)n_b;
             // exact integer numerator; 64-bit, because n_b * ss reaches 2^31 from n_b = 182 rows of 255s on
             var[c] = (float)((int64_t)n_b * ss[c] - (int64_t)s[c] * s[c]) / ((float)n_b * (float)n_b);
+            if constexpr (UNIT) var[c] += var_add;
         }
     }
     float* o = stats_ep + (int64_t)step * 2 * Kp;
@@ -923,8 +929,8 @@ extern "C" int loc_bn_epoch_stats(const uint8_t* X, int64_t x_pitch, const int32
         loc_set_error("loc_bn_epoch_stats: bad batch=%d n_last=%d n_steps=%d", batch, n_last, n_steps);
         return -1;
     }
-    hipLaunchKernelGGL(bn_epoch_stats_kernel, dim3((Kp / 4 + 127) / 128, n_steps), dim3(128), 0, (hipStream_t)stream,
-                       X, x_pitch, rows_all, batch, n_last, n_steps, K, Kp, stats_ep);
+    hipLaunchKernelGGL(bn_epoch_stats_kernel<false>, dim3((Kp / 4 + 127) / 128, n_steps), dim3(128), 0, (hipStream_t)stream,
+                       X, x_pitch, rows_all, batch, n_last, n_steps, K, Kp, stats_ep, 0.f);
     LOC_CHECK_LAUNCH();
     hipLaunchKernelGGL(bn_epoch_finish_kernel, dim3((Kp + 255) / 256), dim3(256), 0, (hipStream_t)stream, K, Kp,
                        n_steps, stats_ep, gamma, beta, mov_mean, mov_var, bn4);
@@ -941,8 +947,8 @@ extern "C" int loc_bn_epoch_stats_only(const uint8_t* X, int64_t x_pitch, const 
         loc_set_error("loc_bn_epoch_stats_only: bad batch=%d n_last=%d n_steps=%d", batch, n_last, n_steps);
         return -1;
     }
-    hipLaunchKernelGGL(bn_epoch_stats_kernel, dim3((Kp / 4 + 127) / 128, n_steps), dim3(128), 0, (hipStream_t)stream,
-                       X, x_pitch, rows_all, batch, n_last, n_steps, K, Kp, stats_ep);
+    hipLaunchKernelGGL(bn_epoch_stats_kernel<false>, dim3((Kp / 4 + 127) / 128, n_steps), dim3(128), 0, (hipStream_t)stream,
+                       X, x_pitch, rows_all, batch, n_last, n_steps, K, Kp, stats_ep, 0.f);
     LOC_CHECK_LAUNCH();
     return 0;
 }
@@ -954,6 +960,49 @@ extern "C" int loc_bn_epoch_finish(int n_steps, int K, int Kp, const float* gamm
     LOC_CHECK_LAUNCH();
     return 0;
 }
+
+// --dosage forms of the two entry points above (trailing argument: the fixed-point unit of X, LOC_DOSAGE_UNIT; 1 = the GT
+// kernels themselves).  Moving statistics and bn4 then run in q units with the compensated variance.
+static int bn_epoch_stats_unit_launch(const uint8_t* X, int64_t x_pitch, const int32_t* rows_all, int batch, int n_last,
+                                      int n_steps, int K, int Kp, float* stats_ep, int unit, void* stream) {
+    if (unit == 1) {
+        hipLaunchKernelGGL(bn_epoch_stats_kernel<false>, dim3((Kp / 4 + 127) / 128, n_steps), dim3(128), 0, (hipStream_t)stream,
+                           X, x_pitch, rows_all, batch, n_last, n_steps, K, Kp, stats_ep, 0.f);
+    } else {
+        hipLaunchKernelGGL(bn_epoch_stats_kernel<true>, dim3((Kp / 4 + 127) / 128, n_steps), dim3(128), 0, (hipStream_t)stream,
+                           X, x_pitch, rows_all, batch, n_last, n_steps, K, Kp, stats_ep, loc_bn_var_add(unit));
+    }
+    LOC_CHECK_LAUNCH();
+    return 0;
+}
+
+static bool bn_unit_ok(int unit) { return unit >= 1 && unit <= LOC_DOSAGE_UNIT; }
+
+extern "C" int loc_bn_epoch_stats_unit(const uint8_t* X, int64_t x_pitch, const int32_t* rows_all, int batch, int n_last,
+                                       int n_steps, int K, int Kp, const float* gamma, const float* beta,
+                                       float* mov_mean, float* mov_var, float* stats_ep, float* bn4, int unit, void* stream) {
+    if (batch < 1 || batch > LOC_BIG_BATCH_MAX || n_last < 1 || n_last > batch || n_steps < 1 || !bn_unit_ok(unit)) {
+        loc_set_error("loc_bn_epoch_stats_unit: bad batch=%d n_last=%d n_steps=%d unit=%d", batch, n_last, n_steps, unit);
+        return -1;
+    }
+    int rc = bn_epoch_stats_unit_launch(X, x_pitch, rows_all, batch, n_last, n_steps, K, Kp, stats_ep, unit, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(bn_epoch_finish_kernel, dim3((Kp + 255) / 256), dim3(256), 0, (hipStream_t)stream, K, Kp,
+                       n_steps, stats_ep, gamma, beta, mov_mean, mov_var, bn4);
+    LOC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int loc_bn_epoch_stats_only_unit(const uint8_t* X, int64_t x_pitch, const int32_t* rows_all, int batch, int n_last,
+                                            int n_steps, int K, int Kp, float* stats_ep, int unit, void* stream) {
+    if (batch < 1 || batch > LOC_BIG_BATCH_MAX || n_last < 1 || n_last > batch || n_steps < 1 || !bn_unit_ok(unit)) {
+        loc_set_error("loc_bn_epoch_stats_only_unit: bad batch=%d n_last=%d n_steps=%d unit=%d", batch, n_last, n_steps, unit);
+        return -1;
+    }
+    return bn_epoch_stats_unit_launch(X, x_pitch, rows_all, batch, n_last, n_steps, K, Kp, stats_ep, unit, stream);
+}
+
+extern "C" float loc_bn_var_add(int unit) { return (float)(unit * unit - 1) * BN_EPS; }
 
 extern "C" int loc_bn_infer_scale_shift(int K, int Kp, const float* gamma, const float* beta, const float* mov_mean,
                                         const float* mov_var, float* out4, void* stream) {

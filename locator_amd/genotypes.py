@@ -612,6 +612,161 @@ def read_matrix(path):
     return gt, samples
 
 
+# ------------------------------------------------------------------ --dosage
+DOSAGE_UNIT = 63          # include/locator_hip.h LOC_DOSAGE_UNIT: q = rint(fp32(d) * 63), 0..126
+Q_MISSING = 255           # host form of a missing value in a q matrix (variants, samples)
+DOSAGE_LO, DOSAGE_HI = -0.001, 2.001      # accepted range of an input dosage; clamped to [0, 2] after the check
+
+
+def _dosage_value(tok, field):
+    """One sample's DS or GP subfield -> dosage as a Python float (NaN = missing)."""
+    if tok == "" or tok == ".":
+        return float("nan")
+    if field == "DS":
+        return float(tok)
+    gp = tok.split(",")
+    if len(gp) != 3:
+        if all(g == "." for g in gp):
+            return float("nan")
+        raise ValueError(f"GP holds {len(gp)} values (3 expected for a diploid biallelic call)")
+    if any(g == "." for g in gp):
+        return float("nan")
+    return float(gp[1]) + 2.0 * float(gp[2])
+
+
+def read_vcf_dosage(path, field="DS"):
+    """--dosage: the expected alt-allele dosage of every call from FORMAT/DS, or from FORMAT/GP as GP1 + 2 GP2, at the field's
+    position in each record's FORMAT (which may differ from record to record).  '.' = missing (NaN).  Records with more than
+    one ALT allele are dropped (their number is returned as 'multiallelic_dropped').  A record without the field, or a value
+    outside [-0.001, 2.001], raises ValueError naming the record and the sample; values are clamped to [0, 2] after that check.
+    Returns {'calldata/DS': float32 (variants, samples), 'samples', 'variants/POS', 'multiallelic_dropped'}."""
+    if field not in ("DS", "GP"):
+        raise ValueError(f"--dosage takes DS or GP (got {field!r})")
+    opener = gzip.open if str(path).endswith(".gz") else open
+    samples, rows, pos = None, [], []
+    dropped = 0
+    with opener(path, "rt") as fh:
+        for line in fh:
+            if line.startswith("##"):
+                continue
+            line = line.rstrip("\n")
+            if line.startswith("#CHROM"):
+                samples = np.array(line.split("\t")[9:], dtype=object)
+                continue
+            if not line:
+                continue
+            f = line.split("\t")
+            where = f"{path}: record {f[0]}:{f[1]}"
+            if "," in f[4]:
+                dropped += 1
+                continue
+            keys = f[8].split(":") if len(f) > 8 else []
+            if field not in keys:
+                raise ValueError(f"{where} has no FORMAT/{field} (FORMAT is {f[8] if len(f) > 8 else 'absent'})")
+            at = keys.index(field)
+            vals = np.empty(len(f) - 9, np.float64)
+            for i, cell in enumerate(f[9:]):
+                sub = cell.split(":")
+                try:
+                    vals[i] = _dosage_value(sub[at] if at < len(sub) else ".", field)
+                except ValueError as e:
+                    raise ValueError(f"{where}, sample {samples[i] if samples is not None else i}: {field} {cell!r}: {e}") \
+                        from None
+            bad = ~np.isnan(vals) & ((vals < DOSAGE_LO) | (vals > DOSAGE_HI))
+            if bad.any():
+                i = int(np.flatnonzero(bad)[0])
+                raise ValueError(f"{where}, sample {samples[i] if samples is not None else i}: dosage {vals[i]:g} from "
+                                 f"{field} is outside [{DOSAGE_LO}, {DOSAGE_HI}]")
+            rows.append(np.clip(vals, 0.0, 2.0).astype(np.float32))
+            pos.append(int(f[1]))
+    if samples is None:
+        raise ValueError(f"{path}: no #CHROM header line")
+    ds = np.stack(rows, axis=0) if rows else np.zeros((0, len(samples)), np.float32)
+    return {"calldata/DS": ds, "samples": samples, "variants/POS": np.asarray(pos, dtype=np.int32),
+            "multiallelic_dropped": dropped}
+
+
+def read_matrix_dosage(path):
+    """--matrix with --dosage: the same table, values read as float dosages (NA = missing).  Returns (float32 (sites,
+    samples), samples); values outside [-0.001, 2.001] raise ValueError, the rest are clamped to [0, 2]."""
+    import pandas as pd
+    gmat = pd.read_csv(path, sep="\t")
+    samples = np.array(gmat["sampleID"])
+    d = np.array(gmat.drop(labels="sampleID", axis=1), dtype=np.float64).T
+    return check_dosage(d, path), samples
+
+
+def check_dosage(d, where):
+    """Range check of float dosages (NaN = missing) and the clamp to [0, 2]: float32 of the same shape."""
+    d = np.asarray(d, dtype=np.float64)
+    bad = ~np.isnan(d) & ((d < DOSAGE_LO) | (d > DOSAGE_HI))
+    if bad.any():
+        v, s = (int(i) for i in np.argwhere(bad)[0])
+        raise ValueError(f"{where}: dosage {d[v, s]:g} of variant {v}, sample {s} is outside [{DOSAGE_LO}, {DOSAGE_HI}]")
+    return np.clip(d, 0.0, 2.0).astype(np.float32)
+
+
+def dosage_q(d):
+    """Fixed-point dosages: q = rint(fp32(d) * 63) clamped to 0..126, Q_MISSING where d is NaN; uint8 of d's shape.  The
+    device's form (csrc/filter_kernels.hip, dosage_q_dev) makes the same single fp32 product and rounding."""
+    d = np.asarray(d, dtype=np.float32)
+    q = np.clip(np.rint(d * np.float32(DOSAGE_UNIT)), 0, 2 * DOSAGE_UNIT)
+    out = np.where(np.isnan(d), Q_MISSING, q).astype(np.uint8)
+    return out
+
+
+def dosage_site_sums(q):
+    """(sum of q over the called samples int64, number of called samples) per variant of a q matrix."""
+    called = q != Q_MISSING
+    return np.where(called, q, 0).sum(axis=1, dtype=np.int64), called.sum(axis=1)
+
+
+def filter_dosage(q, min_mac=2, max_snps=None, impute_missing=False, rng=np.random, verbose=True):
+    """filter_snps for a q matrix (variants, samples) uint8 (dosage_q): keep a site iff, over its called samples,
+    S = sum(q) >= 63 * min_mac, S > 0 and S < 126 * n_called (not monomorphic).  Missing values become 0, or with
+    impute_missing 63 * Binomial(2, af), af = S / (126 n_called), drawn from `rng` once per missing value in variant-major
+    order as replace_md draws.  Then the optional random subset of max_snps sites, as filter_snps.  Returns uint8 (sites,
+    samples) in q units."""
+    if verbose:
+        print("filtering SNPs")
+    q = np.asarray(q, dtype=np.uint8)
+    S, n_called = dosage_site_sums(q)
+    keep = (S >= DOSAGE_UNIT * int(min_mac)) & (S > 0) & (S < 2 * DOSAGE_UNIT * n_called)
+    ac = q[keep]
+    missing = ac == Q_MISSING
+    ac = np.where(missing, 0, ac).astype(np.uint8)
+    if impute_missing and missing.any():
+        af = S[keep] / (2.0 * DOSAGE_UNIT * n_called[keep])
+        for i, j in np.argwhere(missing):
+            ac[i, j] = DOSAGE_UNIT * rng.binomial(2, af[i])
+    if max_snps is not None:
+        pick = rng.choice(range(ac.shape[0]), max_snps, replace=False)
+        ac = ac[pick, :]
+    if verbose:
+        print("running on " + str(len(ac)) + " genotypes after filtering\n\n\n")
+    return np.ascontiguousarray(ac)
+
+
+def write_dosage_zarr(path, ds, chunk_variants=65536, compressor=None):
+    """calldata/DS float32 (variants, samples) into an existing callset store (write_callset_zarr), as `allel.vcf_to_zarr`
+    lays it out when asked for the field (NaN = missing)."""
+    ds = np.asarray(ds, dtype=np.float32)
+    write_zarr_array(os.path.join(path, "calldata", "DS"), ds, (chunk_variants, ds.shape[1]), compressor)
+
+
+def zarr_dosage(callset, where):
+    """The calldata/DS array of a store, or SystemExit naming it.  Only float32 (variants, samples) is accepted."""
+    try:
+        ds = callset["calldata/DS"]
+    except KeyError:
+        raise SystemExit(f"--dosage: {where} has no calldata/DS array (expected dosages, float32 (variants, samples))") \
+            from None
+    if len(ds.shape) != 2 or np.dtype(ds.dtype) != np.float32:
+        raise SystemExit(f"--dosage: {where}: calldata/DS is {np.dtype(ds.dtype)} {tuple(ds.shape)}, expected float32 "
+                         "(variants, samples)")
+    return ds
+
+
 # ------------------------------------------------------------------ allel.GenotypeArray subset
 def count_alleles(gt, max_allele=None):
     """(variants, max_allele+1) int32 counts of called alleles; max_allele defaults to the data's max."""

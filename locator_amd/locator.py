@@ -20,8 +20,8 @@ Deliberate, documented deviations:
     128 or 256 and --nlayers >= 4 with dropout; above 128 the step is correct but not tuned) and --width to 1024 (above 512: per-layer kernels);
   * extra flags --gpus / --fits_per_gpu / --unit_timeout / --no_graph / --no_chain / --net_seed / --load_weights / --predict_mode / --predict_packed / --predict_pieces (recorded at
     the end of params.json), --phased (one prediction per haplotype of phased calls, after scripts/locator_phased.py) and
-    --keep_model (a {stem}.model.npz that `python -m locator_amd.predict` applies to new genotypes), both recorded in
-    params.json only when given.
+    --keep_model (a {stem}.model.npz that `python -m locator_amd.predict` applies to new genotypes) and --dosage (fit on
+    imputed dosages, FORMAT/DS or GP, in fixed point: DESIGN.md section 3), each recorded in params.json only when given.
 """
 from __future__ import annotations
 
@@ -138,6 +138,10 @@ def build_parser():
                    help="write {stem}.model.npz next to where --keep_weights writes {stem}.weights.npz: the weights plus the "
                         "site (CHROM, POS, REF, ALT) of every input column, the coordinate normalisation and the run's "
                         "parameters - what `python -m locator_amd.predict` needs to place new samples without training")
+    p.add_argument("--dosage", default=argparse.SUPPRESS, nargs="?", const="DS", choices=("DS", "GP"),
+                   help="fit on expected alt-allele dosages instead of GT calls: FORMAT/DS (bare --dosage) or FORMAT/GP "
+                        "(GP1 + 2 GP2) of a --vcf, calldata/DS of a --zarr, or float values of a --matrix; stored as "
+                        "rint(63 d), at most 1/126 of an allele off")
     return p
 
 
@@ -156,6 +160,8 @@ def _setup(argv=None):
         with open(args.load_params) as fh:
             merged.update(json.load(fh))
         args = argparse.Namespace(**merged)
+    if getattr(args, "dosage", None) is not None:
+        args.dosage_unit = G.DOSAGE_UNIT        # recorded with the flag: the fixed-point unit of the genotype matrix
     if args.seed is not None:
         np.random.seed(args.seed)
     if args.gpu_number is not None:
@@ -184,6 +190,11 @@ def _phased(a=None):
 
 def _keep_model(a=None):
     return bool(getattr(args if a is None else a, "keep_model", False))
+
+
+def _dosage(a=None):
+    """--dosage: the FORMAT field read ('DS' or 'GP'), None without the flag."""
+    return getattr(args if a is None else a, "dosage", None)
 
 
 def row_ids(samples):
@@ -229,6 +240,64 @@ def _phased_preflight():
         _PRELOADED = (args.vcf, vcf["calldata/GT"], vcf["samples"], vcf)
 
 
+_PRELOADED_DOSAGE = None      # (path, read_vcf_dosage dict) of the VCF that _dosage_preflight has already read
+
+
+def _dosage_preflight():
+    """--dosage refusals, before any worker or device starts.  A VCF is read here (every record must hold the field) and
+    kept for the prologue."""
+    global _PRELOADED_DOSAGE
+    _PRELOADED_DOSAGE = None
+    field = _dosage()
+    if field is None:
+        return
+    if _phased():
+        raise SystemExit("--dosage cannot be combined with --phased: a dosage has no haplotypes")
+    if getattr(args, "predict_packed", False):
+        raise SystemExit("--dosage cannot be combined with --predict_packed: the 2-bit packed matrix holds values 0..3, "
+                         "dosages are stored as 0..126")
+    if _keep_model():
+        raise SystemExit("--dosage cannot be combined with --keep_model: kept models query hard calls only")
+    if args.zarr is not None:
+        if field != "DS":
+            raise SystemExit("--dosage GP: a zarr store is read from calldata/DS only; use --dosage DS")
+        G.zarr_dosage(G.open_group(args.zarr, mode="r"), args.zarr)
+    elif args.vcf is not None:
+        print("reading VCF")
+        try:
+            vcf = G.read_vcf_dosage(args.vcf, field)
+        except ValueError as e:
+            raise SystemExit(f"--dosage {field}: {e}") from None
+        _PRELOADED_DOSAGE = (args.vcf, vcf)
+    elif args.matrix is not None and field != "DS":
+        raise SystemExit("--dosage GP: a --matrix holds one value per site and sample; use --dosage DS")
+
+
+def _load_dosages():
+    """--dosage form of load_genotypes: the fixed-point matrix q (variants, samples) uint8 (genotypes.dosage_q, 255 =
+    missing) and the sample IDs."""
+    global _PRELOADED_DOSAGE
+    if args.zarr is not None:
+        print("reading zarr")
+        callset = G.open_group(args.zarr, mode="r")
+        d = G.check_dosage(np.asarray(G.zarr_dosage(callset, args.zarr)[:]), args.zarr + ": calldata/DS")
+        return G.dosage_q(d), np.asarray(callset["samples"][:])
+    if args.vcf is not None:
+        loaded, _PRELOADED_DOSAGE = _PRELOADED_DOSAGE, None
+        if loaded is not None and loaded[0] == args.vcf:
+            vcf = loaded[1]
+        else:
+            print("reading VCF")
+            vcf = G.read_vcf_dosage(args.vcf, _dosage())
+        if vcf["multiallelic_dropped"]:
+            print(f"--dosage: dropped {vcf['multiallelic_dropped']} record(s) with more than one ALT allele")
+        return G.dosage_q(vcf["calldata/DS"]), vcf["samples"]
+    if args.matrix is not None:
+        d, samples = G.read_matrix_dosage(args.matrix)
+        return G.dosage_q(d), samples
+    raise SystemExit("one of --zarr, --vcf or --matrix is required")
+
+
 # ------------------------------------------------------------------ ingest (locator.py:187-308)
 def load_genotypes():
     """(variants, samples, 2) int8 calls and the sample IDs from whichever of --zarr / --vcf / --matrix was given
@@ -236,6 +305,8 @@ def load_genotypes():
     identity of every input variant is read too (_VARIANTS)."""
     global _VARIANTS
     _VARIANTS = None
+    if _dosage() is not None:
+        return _load_dosages()
     if args.zarr is not None:
         print("reading zarr")
         callset = G.open_group(args.zarr, mode="r")
@@ -329,6 +400,8 @@ def replace_md(genotypes):
 def filter_snps(genotypes, sites=False):
     """--phased: the same filters on the haplotype view (V, 2N, 1): the same sites pass, the matrix holds 0/1 per
     haplotype row.  sites=True: (matrix, input variant index of every row) - no other draw than without it."""
+    if _dosage() is not None:
+        return G.filter_dosage(genotypes, min_mac=args.min_mac, max_snps=args.max_SNPs, impute_missing=args.impute_missing)
     if _phased():
         genotypes = G.haplotypes(genotypes)
     return G.filter_snps(genotypes, min_mac=args.min_mac, max_snps=args.max_SNPs,
@@ -402,9 +475,10 @@ class Model:
 
     def _build(self, X, Y):
         from .net import LocatorNet
+        extra = {"unit": G.DOSAGE_UNIT} if _dosage() is not None else {}
         self.net = LocatorNet(X, Y, self.n_snps, self.width, self.nlayers, self.dropout_prop, seed=self.seed,
                               replicate=self.replicate, device=self.device,
-                              **predict_settings(args))
+                              **predict_settings(args), **extra)
         return self.net
 
     def predict(self, gen):
@@ -808,12 +882,19 @@ def _fit_unit_body(unit, device="cuda:0"):
         shape = unit["gt_shape"]
         nbytes = int(np.prod(shape, dtype=np.int64))
         pin = unit.pop("gt_pin")
-        gt_dev = pin[:nbytes].to(device, non_blocking=True).view(torch.int8).view(*shape)
+        if _dosage(args) is not None:          # the window's calldata/DS: float32 [variants][samples]
+            nbytes *= 4
+            gt_dev = pin[:nbytes].to(device, non_blocking=True).view(torch.float32).view(*shape)
+        else:
+            gt_dev = pin[:nbytes].to(device, non_blocking=True).view(torch.int8).view(*shape)
         if unit.get("phased"):
             gt_dev = gt_dev.view(shape[0], shape[1] * shape[2], 1)        # [variants][2N haplotypes][1]
         train, test, pred = unit["train"], unit["test"], unit["pred"]
         order = np.concatenate([np.asarray(train), np.asarray(test), np.asarray(pred)]).astype(np.int32)
-        if _keep_model(args):
+        if _dosage(args) is not None:
+            from .net import filter_dosage_device
+            X, K = filter_dosage_device(gt_dev, order, args.min_mac)
+        elif _keep_model(args):
             X, K, keep = filter_snps_device(gt_dev, order, args.min_mac, return_keep=True)
             idx = np.flatnonzero(keep)
             host = pin.numpy()[:nbytes].view(np.int8).reshape(shape)
@@ -910,11 +991,12 @@ def _read_window(unit):
     (net.filter_snps_device in _fit_unit): the host phase of a 150,000-variant window drops from 0.68 s (NumPy allele counts +
     boolean indexing + three transposed copies of a 230 MB slice) to the read itself."""
     a, b = unit["window"]
-    gt = G.open_group(unit["zarr"], mode="r")["calldata/GT"]
+    dosage = _dosage(unit["args"]) is not None
+    gt = G.open_group(unit["zarr"], mode="r")["calldata/DS" if dosage else "calldata/GT"]
     shape = (max(min(b, gt.shape[0]) - a, 0),) + tuple(gt.shape[1:])
-    nbytes = int(np.prod(shape, dtype=np.int64))
+    nbytes = int(np.prod(shape, dtype=np.int64)) * (4 if dosage else 1)
     pin = _pin_take(nbytes)
-    view = pin.numpy()[:nbytes].view(np.int8).reshape(shape)
+    view = pin.numpy()[:nbytes].view(np.float32 if dosage else np.int8).reshape(shape)
     gt.read_into(view, a, a + shape[0])
     unit["gt_pin"], unit["gt_shape"] = pin, shape
     return unit
@@ -928,6 +1010,8 @@ def _load_window_on_loader_thread(unit, a):
     u = dict(unit)
     u["args"] = a
     if torch.cuda.is_available() and not getattr(a, "host_filter", False):
+        if _dosage(a) is not None:
+            return _read_window(u)          # calldata/DS float32 (variants, samples): zarr_dosage checked it in the preflight
         gt = G.open_group(u["zarr"], mode="r")["calldata/GT"]
         # the device filter takes the store's calls as they are: int8 [variants][samples][ploidy].  Any other dtype or
         # rank goes the host way (np.asarray(..., dtype=int8) as load_genotypes does) instead of failing every window
@@ -994,8 +1078,13 @@ def _load_window(unit, draw_split=False, individuals=None):
     if "traingen" in unit:
         return unit
     a, b = unit["window"]
-    gt = G.open_group(unit["zarr"], mode="r")["calldata/GT"]
-    genotypes = np.asarray(gt[a:b, :, :], dtype=np.int8)
+    dosage = _dosage(unit["args"] if "args" in unit else args) is not None
+    if dosage:
+        ds = G.open_group(unit["zarr"], mode="r")["calldata/DS"]
+        genotypes = G.dosage_q(G.check_dosage(np.asarray(ds[a:b]), f"{unit['zarr']}: calldata/DS"))
+    else:
+        gt = G.open_group(unit["zarr"], mode="r")["calldata/GT"]
+        genotypes = np.asarray(gt[a:b, :, :], dtype=np.int8)
     keep_model = "variants" in unit
     if draw_split:                                   # eager path: reference order sort -> normalise -> filter -> split
         meanlong, sdlong, meanlat, sdlat, locs = row_locs(unit["samples"] if individuals is None else individuals,
@@ -1004,9 +1093,12 @@ def _load_window(unit, draw_split=False, individuals=None):
         train, test, pred = split_rows(locs, args.train_split)
         unit.update(sdlong=sdlong, meanlong=meanlong, sdlat=sdlat, meanlat=meanlat)
     else:
-        calls = G.haplotypes(genotypes) if unit.get("phased") else genotypes
-        ac = G.filter_snps(calls, min_mac=unit["args"].min_mac if "args" in unit else args.min_mac, verbose=False,
-                           sites=keep_model)
+        min_mac = unit["args"].min_mac if "args" in unit else args.min_mac
+        if dosage:
+            ac = G.filter_dosage(genotypes, min_mac=min_mac, verbose=False)
+        else:
+            calls = G.haplotypes(genotypes) if unit.get("phased") else genotypes
+            ac = G.filter_snps(calls, min_mac=min_mac, verbose=False, sites=keep_model)
         train, test, pred, locs = unit["train"], unit["test"], unit["pred"], unit["locs"]
     if keep_model:
         ac, idx = ac
@@ -1050,7 +1142,7 @@ def _prologue(force_full=False):
         samples = np.asarray(callset["samples"][:])
 
         class _Shape:
-            shape = tuple(callset["calldata/GT"].shape)
+            shape = tuple((G.zarr_dosage(callset, args.zarr) if _dosage() is not None else callset["calldata/GT"]).shape)
         sample_data, locs = sort_samples(samples, _Shape())
         meanlong, sdlong, meanlat, sdlat, locs = normalize_locs(locs)
         split_indices(locs, args.train_split)        # --phased: the same draw (over individuals)
@@ -1110,6 +1202,7 @@ def main(argv=None):
         # prologue, and every worker is then a fork + one device context (replicates.warm_start)
         replicates.warm_start("forkserver")
     _setup(argv)
+    _dosage_preflight()             # first: it refuses --phased with --dosage
     _phased_preflight()
 
     pool = None
@@ -1232,6 +1325,10 @@ def _jacknife(ac, traingen, testgen, trainlocs, testlocs, predgen, pred, samples
     if _phased():                                         # 0/1 haplotype rows: frequency over n_rows alleles, Binomial(1, af)
         af = ac.sum(axis=1) / ac.shape[1]
         draws = jacknife_draws(base, af, args.nboots, args.jacknife_prop, ploidy=1)
+    elif _dosage() is not None:                           # q units: af = sum(q) / (126 n), values 63 Binomial(2, af)
+        af = ac.sum(axis=1, dtype=np.int64) / (ac.shape[1] * 2 * G.DOSAGE_UNIT)
+        draws = [(sites, vals * G.DOSAGE_UNIT)
+                 for sites, vals in jacknife_draws(base, af, args.nboots, args.jacknife_prop)]
     else:
         af = ac.sum(axis=1) / (ac.shape[1] * 2)
         draws = jacknife_draws(base, af, args.nboots, args.jacknife_prop)

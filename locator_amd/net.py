@@ -67,7 +67,7 @@ class LocatorNet:
     Adam, Euclidean loss — the model of locator.py:311-327, resident on one GPU."""
 
     def __init__(self, X, Y, K, width=256, nlayers=10, dropout_prop=0.25, seed=0, replicate=0, device="cuda:0",
-                 predict_pieces=3, predict_digits=3, tuning=None):
+                 predict_pieces=3, predict_digits=3, tuning=None, unit=1):
         """predict_digits: int8 digit planes per weight in the many-row inference forward: 0 = AUTO (the default of the
         command line): two planes (16-bit fixed point against each unit's largest weight) while the dynamic-range guard
         of the weights allows it (include/locator_hip.h, LOC_GUARD_*: measured 5e-5 relative on the predictions of the
@@ -76,7 +76,9 @@ class LocatorNet:
         predict_pieces: bf16 pieces per weight where the int8 GEMM does not apply - few rows, genotypes above 127 -
         (3 = exact fp32 products; 1 or 2 trade accuracy for speed, -1 keeps every row block on the 32-row fp32-MFMA
         kernel).  tuning: dict of loc_tuning fields (include/locator_hip.h) - speed hints and measurement switches,
-        never results."""
+        never results.  unit: the fixed-point unit of X (1 = allele counts; --dosage: LOC_DOSAGE_UNIT = 63, X holds
+        q = 63 d and the model is the one on d = q / 63: BatchNorm statistics in q units with the compensated variance,
+        converted back to dosage units by export_params / import_params - DESIGN.md section 3)."""
         require_gpu()
         self.lib = _lib.load()
         self.device = torch.device(device)
@@ -85,6 +87,10 @@ class LocatorNet:
         assert X.dtype == torch.uint8 and X.is_cuda and X.shape[1] == self.d.Kp and X.is_contiguous()
         assert Y.dtype == torch.float32 and Y.is_cuda and Y.shape[1] == 2 and Y.is_contiguous()
         self.X, self.Y = X, Y
+        self.unit = int(unit)
+        if not 1 <= self.unit <= 63:
+            raise ValueError(f"unit must be in 1..63 (got {unit})")
+        self.var_add = float(self.lib.loc_bn_var_add(self.unit)) if self.unit != 1 else 0.0
         self.drop_p = float(dropout_prop)
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.replicate = int(replicate)
@@ -206,7 +212,7 @@ class LocatorNet:
         self.adam_m.zero_()
         self.adam_v.zero_()
         self._sec("gamma", d.K).fill_(1.0)
-        self._sec("mov_var", d.K).fill_(1.0)
+        self._sec("mov_var", d.K).fill_(1.0 if self.unit == 1 else float(np.float32(self.unit * self.unit) + np.float32(self.var_add)))
         sid = lambda layer: (self.replicate << 16) | layer
         p = self.params.data_ptr()
         st = _stream()
@@ -249,6 +255,10 @@ class LocatorNet:
         if with_moving:
             out["mov_mean"] = flat[lay.mov_mean:lay.mov_mean + d.K].cpu().numpy()
             out["mov_var"] = flat[lay.mov_var:lay.mov_var + d.K].cpu().numpy()
+            if self.unit != 1:        # q units with the compensated variance -> dosage units
+                u = float(self.unit)
+                out["mov_mean"] = (out["mov_mean"].astype(np.float64) / u).astype(np.float32)
+                out["mov_var"] = ((out["mov_var"].astype(np.float64) - self.var_add) / (u * u)).astype(np.float32)
         return out
 
     def export_params(self):
@@ -277,8 +287,13 @@ class LocatorNet:
         flat[lay.gamma:lay.gamma + d.K] = f32(p["gamma"])
         flat[lay.beta:lay.beta + d.K] = f32(p["beta"])
         if with_moving:
-            flat[lay.mov_mean:lay.mov_mean + d.K] = f32(p["mov_mean"])
-            flat[lay.mov_var:lay.mov_var + d.K] = f32(p["mov_var"])
+            mm, mv = p["mov_mean"], p["mov_var"]
+            if self.unit != 1:        # dosage units -> q units with the compensated variance
+                u = float(self.unit)
+                mm = np.asarray(mm, np.float64) * u
+                mv = np.asarray(mv, np.float64) * (u * u) + self.var_add
+            flat[lay.mov_mean:lay.mov_mean + d.K] = f32(mm)
+            flat[lay.mov_var:lay.mov_var + d.K] = f32(mv)
 
     def check_params(self, p, with_moving=True):
         """Shapes of an oracle-format parameter dict against this net, BEFORE any device call: the swizzle kernel
@@ -310,6 +325,8 @@ class LocatorNet:
         mask: uint8 device tensor [32*Hp] of keep flags ([32*Kp] when nlayers == 1: mask_width) or None, loss_out:
         1-element float32 view.
         bn_ready / bn_next: epoch-level BN statistics (see epoch_bn_stats)."""
+        if self.unit != 1 and not bn_ready:
+            raise ValueError("a dosage net (unit != 1) takes its BatchNorm statistics from epoch_bn_stats (bn_ready=True)")
         self.params_changed()
         net = self._net or self.cnet()
         _lib.check(self.lib.loc_train_step(C.byref(net), _ptr(rows), int(n_b), int(t_off), _ptr(mask),
@@ -342,6 +359,13 @@ class LocatorNet:
         self.params_changed()
         net = self._net or self.cnet()
         d, lay, P = self.d, self.lay, self.params.data_ptr()
+        if self.unit != 1:
+            _lib.check(self.lib.loc_bn_epoch_stats_unit(self.X.data_ptr(), self.X.stride(0), _ptr(rows_all), int(batch),
+                                                        int(n_last), int(n_steps), d.K, d.Kp, P + 4 * lay.gamma,
+                                                        P + 4 * lay.beta, P + 4 * lay.mov_mean, P + 4 * lay.mov_var,
+                                                        _ptr(stats_ep), self.lib.loc_workspace_bn4(C.byref(net)), self.unit,
+                                                        _stream()), "loc_bn_epoch_stats_unit")
+            return
         _lib.check(self.lib.loc_bn_epoch_stats(self.X.data_ptr(), self.X.stride(0), _ptr(rows_all), int(batch),
                                                int(n_last), int(n_steps), d.K, d.Kp, P + 4 * lay.gamma,
                                                P + 4 * lay.beta, P + 4 * lay.mov_mean, P + 4 * lay.mov_var,
@@ -351,6 +375,11 @@ class LocatorNet:
     def epoch_bn_stats_only(self, rows_all, batch, n_last, n_steps, stats_ep):
         """Only the batch statistics of an epoch's minibatches (loc_bn_epoch_stats_only): nothing of the model changes."""
         d = self.d
+        if self.unit != 1:
+            _lib.check(self.lib.loc_bn_epoch_stats_only_unit(self.X.data_ptr(), self.X.stride(0), _ptr(rows_all), int(batch),
+                                                             int(n_last), int(n_steps), d.K, d.Kp, _ptr(stats_ep), self.unit,
+                                                             _stream()), "loc_bn_epoch_stats_only_unit")
+            return
         _lib.check(self.lib.loc_bn_epoch_stats_only(self.X.data_ptr(), self.X.stride(0), _ptr(rows_all), int(batch), int(n_last),
                                                     int(n_steps), d.K, d.Kp, _ptr(stats_ep), _stream()), "loc_bn_epoch_stats_only")
 
@@ -522,4 +551,29 @@ def filter_snps_device(gt, sample_order, min_mac=2, return_keep=False):
                                             X.stride(0), _stream()), "loc_filter_snps_rows")
     if return_keep:
         return X, K, keep.cpu().numpy()
+    return X, K
+
+
+def filter_dosage_device(ds, sample_order, min_mac=2):
+    """--dosage form of filter_snps_device: ds float32 device tensor [n_variants][n_samples] (the window's calldata/DS slice,
+    NaN = missing) -> (X uint8 [len(order)][Kp] in q units, K), bit-identical to genotypes.filter_dosage without
+    --impute_missing / --max_SNPs + the NumPy transposes (loc_dosage_flags, loc_dosage_rows).  One host synchronisation."""
+    lib = _lib.load()
+    assert ds.dtype == torch.float32 and ds.is_cuda and ds.is_contiguous() and ds.dim() == 2
+    V, N = (int(v) for v in ds.shape)
+    dev = ds.device
+    keep = torch.empty(V, dtype=torch.uint8, device=dev)
+    pos = torch.empty(V, dtype=torch.int32, device=dev)
+    nk = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.loc_dosage_flags(_ptr(ds), V, N, int(min_mac), _ptr(keep), _ptr(pos), _ptr(nk), _stream()),
+               "loc_dosage_flags")
+    K = int(nk.item())
+    order = torch.as_tensor(np.asarray(sample_order, dtype=np.int32)).to(dev)
+    if len(order) and (int(order.min()) < 0 or int(order.max()) >= N):
+        raise ValueError(f"sample_order holds rows outside 0..{N - 1}")
+    Kp = (max(K, 1) + 31) // 32 * 32
+    X = torch.zeros((len(order), Kp), dtype=torch.uint8, device=dev)
+    if K > 0:
+        _lib.check(lib.loc_dosage_rows(_ptr(ds), V, N, _ptr(keep), _ptr(pos), _ptr(order), len(order), _ptr(X), X.stride(0),
+                                       _stream()), "loc_dosage_rows")
     return X, K
