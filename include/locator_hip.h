@@ -10,6 +10,9 @@
  * Conventions
  *   - extern "C", plain pointers and sizes; no C++ or torch types.
  *   - every pointer is a DEVICE pointer unless the name starts with `h_`.
+ *   - locator_amd/_abi.py derives the Python binding from this text: one declaration
+ *     per `;`, every parameter named, scalar types from int, int32_t, uint32_t, int64_t,
+ *     uint64_t, float and double, block comments only.
  *   - the caller owns every buffer; nothing here allocates or frees device memory.
  *   - all work is enqueued on `stream` (a hipStream_t passed as void*); no
  *     implicit synchronisation.  The library reads no environment variables and
@@ -217,6 +220,9 @@ typedef struct loc_gb_tail {
 
 const char* loc_last_error(void);
 int loc_version(void);
+/* LOC_GEMM_MIN_ROWS / LOC_GEMM_I8_MIN_ROWS for callers that cannot expand a macro */
+int loc_gemm_min_rows(int pieces);
+int loc_gemm_i8_min_rows(int digits);
 
 /* ---- layout helpers (host only) ---- */
 int loc_make_dims(int K, int H, int L, loc_dims* out);
@@ -225,6 +231,9 @@ int64_t loc_w1s_index(int h, int k, int Hp);
 int64_t loc_workspace_floats(const loc_dims* d);
 /* the same for --batch_size up to `batch` rows (> LOC_MAX_BATCH: one activation slot holds ceil(batch / 128) * 128 rows) */
 int64_t loc_workspace_floats_batch(const loc_dims* d, int batch);
+/* floats of layer-1 partial-sum scratch inside that workspace: what loc_l1_forward (LOC_MAX_FWD_GRID workgroups x 32 rows)
+ * and the large-M forms (LOC_ROWS_BLOCKS tiles of LOC_ROWS_TILE rows) are sized for; a caller with its own scratch asks here */
+int64_t loc_l1_partial_floats(const loc_dims* d);
 
 /* ---- utility kernels ---- */
 /* Keras glorot_uniform init of one Dense kernel (locator.py:319-325 [K]): logical R x C (in x out),
@@ -376,14 +385,14 @@ int loc_l1_forward_gemm_i8(const uint8_t* X, int64_t x_pitch, const int32_t* row
                            const void* image, int digits, int x_max, const float* b1, float* partial,
                            int64_t partial_floats, float* a1, int target_blocks, const loc_tuning* tune, void* stream);
 /* loc_l1_forward_gemm_i8 (packed != 0: loc_l1_forward_gemm_i8_packed, X / x_pitch then are the packed matrix's) WITHOUT its
- * reduction launch: the SNP-group partial sums stay in `partial` as [*h_groups][ceil(n/128)*128][256] floats and *cvec8
+ * reduction launch: the SNP-group partial sums stay in `partial` as [*h_groups][ceil(n/128)*128][256] floats and *h_cvec8
  * points at the image's 8 x 256 shift-term slices; loc_stack_forward_eval_partial adds them up (+ b1, ELU) in the input
- * stage of the hidden-stack launch - the same association as the reduction kernel, so the same bits.  h_groups and cvec8
+ * stage of the hidden-stack launch - the same association as the reduction kernel, so the same bits.  h_groups and h_cvec8
  * are HOST pointers written before the call returns. */
 int loc_l1_forward_gemm_i8_partial(const uint8_t* X, int64_t x_pitch, int packed, const int32_t* rows, int n,
                                    const loc_dims* d, const void* image, int digits, int x_max, float* partial,
                                    int64_t partial_floats, int target_blocks, const loc_tuning* tune, int* h_groups,
-                                   const float** cvec8, void* stream);
+                                   const float** h_cvec8, void* stream);
 /* Fused: dW1 = xhat^T dZ1, dxhat = dZ1 W1^T -> dgamma/dbeta, Adam on W1/gamma/beta/b1.
  * dW1 and dxhat are never written to memory.  gb_scratch: (Kp/32)*128 floats (per-wave partial
  * sums for dgamma/dbeta, combined in a fixed order by a trailing per-SNP kernel).  If bn_next_stats
@@ -651,11 +660,11 @@ int loc_epoch_callbacks(const float* stats, int steps, int batch, int n_last, in
 int loc_snapshot_if(const loc_cb_state* state, const float* params, float* best, int64_t n, void* stream);
 
 /* thin event helpers so a ctypes host can time a kernel on the stream it runs on */
-int loc_event_create(void** ev);
-int loc_event_create_notiming(void** ev);
+int loc_event_create(void** h_ev);
+int loc_event_create_notiming(void** h_ev);
 int loc_event_destroy(void* ev);
 int loc_event_record(void* ev, void* stream);
-int loc_event_elapsed_ms(void* ev0, void* ev1, float* ms);
+int loc_event_elapsed_ms(void* ev0, void* ev1, float* h_ms);
 
 #ifdef __cplusplus
 }

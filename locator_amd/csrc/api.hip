@@ -18,6 +18,8 @@ void loc_set_error(const char* fmt, ...) {
 
 extern "C" const char* loc_last_error(void) { return g_err; }
 extern "C" int loc_version(void) { return 1; }
+extern "C" int loc_gemm_min_rows(int pieces) { return LOC_GEMM_MIN_ROWS(pieces); }
+extern "C" int loc_gemm_i8_min_rows(int digits) { return LOC_GEMM_I8_MIN_ROWS(digits); }
 
 extern "C" int loc_make_dims(int K, int H, int L, loc_dims* out) {
     if (K < 1 || H < 1 || H > LOC_MAX_WIDTH || L < 1) {
@@ -63,7 +65,7 @@ struct ws_view {
 };
 // scratch of the layer-1 forward partial sums: the 32-row kernel needs grid*32*Hp, the large-M kernel
 // LOC_ROWS_BLOCKS tiles of 128*Hp
-static int64_t partial_floats_of(const loc_dims* d) {
+extern "C" int64_t loc_l1_partial_floats(const loc_dims* d) {
     const int64_t a = (int64_t)LOC_MAX_FWD_GRID * 32 * d->Hp, b = (int64_t)LOC_ROWS_BLOCKS * LOC_ROWS_TILE * d->Hp;
     return a > b ? a : b;
 }
@@ -87,7 +89,7 @@ static ws_view carve(const loc_dims* d, float* ws, int parity = 0, int slot = LO
     v.bn4 = ws;
     v.gbs = v.bn4 + 4 * (int64_t)d->Kp;
     v.partial = v.gbs + 4 * (int64_t)d->Kp;
-    v.partial_floats = partial_floats_of(d);
+    v.partial_floats = loc_l1_partial_floats(d);
     v.acts = v.partial + v.partial_floats + (parity & 1) * per_step;
     v.adrop = v.acts + d->L * blk;
     v.dz = v.adrop + blk;
@@ -97,7 +99,7 @@ static ws_view carve(const loc_dims* d, float* ws, int parity = 0, int slot = LO
 }
 extern "C" int64_t loc_workspace_floats_batch(const loc_dims* d, int batch) {
     const int cap = batch > LOC_BATCH_SLOT ? (batch + 127) / 128 * 128 : LOC_BATCH_SLOT;
-    return 8 * (int64_t)d->Kp + partial_floats_of(d) + 2 * per_step_floats(d, cap) + (int64_t)LOC_PREDICT_CHUNK * d->Hp;
+    return 8 * (int64_t)d->Kp + loc_l1_partial_floats(d) + 2 * per_step_floats(d, cap) + (int64_t)LOC_PREDICT_CHUNK * d->Hp;
 }
 extern "C" int64_t loc_workspace_floats(const loc_dims* d) { return loc_workspace_floats_batch(d, LOC_BATCH_SLOT); }
 
@@ -133,7 +135,7 @@ extern "C" int loc_train_chain_supported(const loc_net* net) {
     const bool in_drop = net->drop_p > 0.f && d->n_pre == 0;
     return d->L >= 2 && net->wht && loc_stack_fused_supported(d->Hp) && loc_l1_chain_supported(d->Hp) &&
            (net->slot_rows <= LOC_ROWS || (net->slot_rows <= LOC_CHAIN_MAX_ROWS && d->Hp == 256)) && !in_drop &&
-           (int64_t)chain_groups_of(net) * 32 * chain_rb_of(net) * d->Hp <= partial_floats_of(d) &&
+           (int64_t)chain_groups_of(net) * 32 * chain_rb_of(net) * d->Hp <= loc_l1_partial_floats(d) &&
            l1_chain_offsets_fit(d) && (net->x_pitch % 16) == 0;
 }
 
@@ -453,25 +455,25 @@ extern "C" int loc_predict(const loc_net* net, const int32_t* rows, int n, float
     return 0;
 }
 
-extern "C" int loc_event_create_notiming(void** ev) {
+extern "C" int loc_event_create_notiming(void** h_ev) {
     hipEvent_t e;
     hipError_t rc = hipEventCreateWithFlags(&e, hipEventDisableTiming);
     if (rc != hipSuccess) { loc_set_error("hipEventCreateWithFlags: %s", hipGetErrorString(rc)); return (int)rc; }
-    *ev = (void*)e;
+    *h_ev = (void*)e;
     return 0;
 }
-extern "C" int loc_event_create(void** ev) {
+extern "C" int loc_event_create(void** h_ev) {
     hipEvent_t e;
     hipError_t rc = hipEventCreate(&e);
     if (rc != hipSuccess) { loc_set_error("hipEventCreate: %s", hipGetErrorString(rc)); return (int)rc; }
-    *ev = (void*)e;
+    *h_ev = (void*)e;
     return 0;
 }
 extern "C" int loc_event_destroy(void* ev) { return (int)hipEventDestroy((hipEvent_t)ev); }
 extern "C" int loc_event_record(void* ev, void* stream) { return (int)hipEventRecord((hipEvent_t)ev, (hipStream_t)stream); }
-extern "C" int loc_event_elapsed_ms(void* ev0, void* ev1, float* ms) {
+extern "C" int loc_event_elapsed_ms(void* ev0, void* ev1, float* h_ms) {
     hipError_t rc = hipEventSynchronize((hipEvent_t)ev1);
-    if (rc == hipSuccess) rc = hipEventElapsedTime(ms, (hipEvent_t)ev0, (hipEvent_t)ev1);
+    if (rc == hipSuccess) rc = hipEventElapsedTime(h_ms, (hipEvent_t)ev0, (hipEvent_t)ev1);
     if (rc != hipSuccess) { loc_set_error("hipEventElapsedTime: %s", hipGetErrorString(rc)); return (int)rc; }
     return 0;
 }

@@ -906,9 +906,9 @@ static int g8_forward(const uint8_t* X, int64_t x_pitch, const int32_t* rows, in
 extern "C" int loc_l1_forward_gemm_i8_partial(const uint8_t* X, int64_t x_pitch, int packed, const int32_t* rows, int n,
                                               const loc_dims* d, const void* image, int digits, int x_max, float* partial,
                                               int64_t partial_floats, int target_blocks, const loc_tuning* tune,
-                                              int* h_groups, const float** cvec8, void* stream) {
-    if (!h_groups || !cvec8) { loc_set_error("loc_l1_forward_gemm_i8_partial: h_groups / cvec8 must not be NULL"); return -1; }
-    *cvec8 = reinterpret_cast<const float*>(image);
+                                              int* h_groups, const float** h_cvec8, void* stream) {
+    if (!h_groups || !h_cvec8) { loc_set_error("loc_l1_forward_gemm_i8_partial: h_groups / h_cvec8 must not be NULL"); return -1; }
+    *h_cvec8 = reinterpret_cast<const float*>(image);
     return g8_forward(X, x_pitch, rows, n, d, image, digits, packed ? 3 : x_max, nullptr, partial, partial_floats, nullptr,
                       target_blocks, tune, packed != 0, stream, h_groups);
 }

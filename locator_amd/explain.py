@@ -140,7 +140,7 @@ def _l1_forward(model, X, device):
 
     import torch
 
-    from . import _lib
+    from . import _abi, _lib
     from .net import LocatorNet, _ptr, _stream
     lib = _lib.load()
     n = int(X.shape[0])
@@ -154,9 +154,9 @@ def _l1_forward(model, X, device):
                                             P + 4 * lay.mov_var, _ptr(bn4), _stream()), "loc_bn_infer_scale_shift")
     rows = torch.arange(n, dtype=torch.int32, device=device)
     a1 = torch.zeros(((n + 127) // 128 * 128, Hp), dtype=torch.float32, device=device)
-    chunk = 16384                                                     # LOC_PREDICT_CHUNK
+    chunk = _abi.LOC_PREDICT_CHUNK
     if lib.loc_l1_rows_supported(Hp, 3):
-        pf = max(512 * 32, 256 * 128) * Hp                            # the workspace's layer-1 partial sums
+        pf = lib.loc_l1_partial_floats(C.byref(d))                    # the workspace's layer-1 partial sums
         partial = torch.empty(pf, dtype=torch.float32, device=device)
         tune = _lib.Tuning()
         for c0 in range(0, n, chunk):

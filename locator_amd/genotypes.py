@@ -21,6 +21,8 @@ import zlib
 
 import numpy as np
 
+from . import _abi
+
 
 # ------------------------------------------------------------------ VCF
 def _parse_gt_fast(fields, n, seps=None):
@@ -613,7 +615,7 @@ def read_matrix(path):
 
 
 # ------------------------------------------------------------------ --dosage
-DOSAGE_UNIT = 63          # include/locator_hip.h LOC_DOSAGE_UNIT: q = rint(fp32(d) * 63), 0..126
+DOSAGE_UNIT = _abi.LOC_DOSAGE_UNIT          # 63: q = rint(fp32(d) * 63), 0..126
 Q_MISSING = 255           # host form of a missing value in a q matrix (variants, samples)
 DOSAGE_LO, DOSAGE_HI = -0.001, 2.001      # accepted range of an input dosage; clamped to [0, 2] after the check
 

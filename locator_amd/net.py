@@ -12,17 +12,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._abi import (LOC_BATCH_SLOT, LOC_BIG_BATCH_MAX, LOC_DOSAGE_UNIT, LOC_GEMM_I8_PACKED_MIN_ROWS, LOC_MAX_BATCH,
+                   LOC_MAX_FWD_GRID, LOC_ROWS)
 
 ALPHA_TAB_LEN = 32769            # beyond this t the Adam bias correction is 1 to fp32 precision
 ADAM_B1, ADAM_B2 = 0.9, 0.999
-LOC_ROWS = 32
-LOC_MAX_BATCH = 128      # include/locator_hip.h: four 32-row blocks per step (the row-block kernels)
-LOC_BIG_BATCH_MAX = 4096 # include/locator_hip.h: --batch_size limit (above 128: row blocks streamed from L2)
-LOC_BATCH_SLOT = 128     # rows per activation slot of the training scratch when batch > 32
-LOC_MAX_FWD_GRID = 512
-LOC_GEMM_MIN_ROWS = {3: 1152, 2: 768, 1: 640}  # include/locator_hip.h, by bf16 pieces
-LOC_GEMM_I8_MIN_ROWS = 512                     # include/locator_hip.h: int8 image + GEMM
-LOC_GEMM_I8_PACKED_MIN_ROWS = 3072             # include/locator_hip.h: rows per chunk from which 2-bit packed genotypes pay
 
 
 def _ptr(t):
@@ -88,8 +82,8 @@ class LocatorNet:
         assert Y.dtype == torch.float32 and Y.is_cuda and Y.shape[1] == 2 and Y.is_contiguous()
         self.X, self.Y = X, Y
         self.unit = int(unit)
-        if not 1 <= self.unit <= 63:
-            raise ValueError(f"unit must be in 1..63 (got {unit})")
+        if not 1 <= self.unit <= LOC_DOSAGE_UNIT:
+            raise ValueError(f"unit must be in 1..{LOC_DOSAGE_UNIT} (got {unit})")
         self.var_add = float(self.lib.loc_bn_var_add(self.unit)) if self.unit != 1 else 0.0
         self.drop_p = float(dropout_prop)
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -400,7 +394,7 @@ class LocatorNet:
         lib, d = self.lib, self.d
         capturing = torch.cuda.is_current_stream_capturing() or bool(in_fit)
         digits = self.predict_digits if self.predict_digits != 0 else 3
-        use_i8 = (self.predict_pieces > 0 and digits > 0 and n >= LOC_GEMM_I8_MIN_ROWS
+        use_i8 = (self.predict_pieces > 0 and digits > 0 and n >= lib.loc_gemm_i8_min_rows(digits)
                   and lib.loc_l1_gemm_i8_supported(d.Hp, digits))
         if use_i8 and self.genotype_max() > 127:
             use_i8 = False
@@ -408,7 +402,7 @@ class LocatorNet:
         need = 0
         if use_i8:
             need = lib.loc_l1_image_i8_bytes(C.byref(d), 3 if self.predict_digits == 0 else digits)
-        elif (self.predict_pieces > 0 and n >= LOC_GEMM_MIN_ROWS.get(self.predict_pieces, 1 << 30)
+        elif (self.predict_pieces > 0 and n >= lib.loc_gemm_min_rows(self.predict_pieces)
               and lib.loc_l1_gemm_supported(d.Hp, self.predict_pieces)):
             need = lib.loc_l1_image_bytes(C.byref(d), self.predict_pieces)
         if guarded:

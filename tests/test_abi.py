@@ -4,11 +4,13 @@ agree with the documented swizzle.  No kernel is launched here."""
 import ctypes as C
 import os
 import re
+import subprocess
+import sys
 
 import numpy as np
 import pytest
 
-from locator_amd import _lib
+from locator_amd import _abi, _lib, genotypes
 
 
 def _header_symbols(repo_root):
@@ -51,6 +53,106 @@ def test_ctypes_structs_follow_the_header_field_for_field(repo_root):
     assert re.findall(r'"([a-z_0-9A-Z]+)"', tstub) == [f[0] for f in _lib.Tuning._fields_]
     # pointer / int64 / int / float members only: the natural-alignment size is what both compilers produce
     assert C.sizeof(_lib.Net) % 8 == 0
+
+
+def test_c_compiler_agrees_with_the_derived_structs(repo_root, tmp_path):
+    """An independent witness of locator_amd/_abi.py: a C program that includes the header prints sizeof and every offsetof /
+    member size of every struct in it (gcc, the host compiler build() needs for libloc_codecs.so); the ctypes classes must
+    agree field by field.  The struct and member names come from this test's own reading of the header, not from _abi."""
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(repo_root, "include", "locator_hip.h")).read(), flags=re.S)
+    structs = {}
+    for name, body in re.findall(r"typedef struct (\w+) \{(.*?)\} \1;", src, flags=re.S):
+        structs[name] = [re.search(r"(\w+)\s*$", piece).group(1)
+                         for decl in body.split(";") if decl.strip() for piece in decl.split(",")]
+    assert list(structs) == ["loc_dims", "loc_layout", "loc_tuning", "loc_net", "loc_gb_tail", "loc_cb_state"]
+    lines = ['#include <stdio.h>', '#include "locator_hip.h"', "int main(void) {"]
+    for name, fields in structs.items():
+        lines.append(f'    printf("{name} %zu\\n", sizeof({name}));')
+        lines += [f'    printf("{name}.{f} %zu %zu\\n", offsetof({name}, {f}), sizeof((({name}*)0)->{f}));' for f in fields]
+    lines += ["    return 0;", "}"]
+    (tmp_path / "witness.c").write_text("\n".join(lines) + "\n")
+    exe = str(tmp_path / "witness")
+    subprocess.check_call(["gcc", "-std=c11", "-Wall", "-I", os.path.join(repo_root, "include"), "-o", exe,
+                           str(tmp_path / "witness.c")])
+    seen = dict(line.split(" ", 1) for line in subprocess.check_output([exe], text=True).splitlines())
+    assert set(_abi.STRUCTS) == set(structs)
+    for name, fields in structs.items():
+        ctype = _abi.STRUCTS[name]
+        assert [f[0] for f in ctype._fields_] == fields, name
+        assert int(seen[name]) == C.sizeof(ctype), name
+        for f in fields:
+            assert seen[f"{name}.{f}"] == f"{getattr(ctype, f).offset} {getattr(ctype, f).size}", (name, f)
+    sizes = {n: int(seen[n]) for n in ("loc_dims", "loc_layout", "loc_tuning", "loc_net", "loc_cb_state")}
+    assert sizes == {"loc_dims": 24, "loc_layout": 112, "loc_tuning": 40, "loc_net": 248, "loc_cb_state": 72}
+    assert seen["loc_net.tune"] == "204 40"
+    assert (_lib.Dims, _lib.Layout, _lib.Tuning, _lib.Net, _lib.CbState) == tuple(
+        _abi.STRUCTS[n] for n in ("loc_dims", "loc_layout", "loc_tuning", "loc_net", "loc_cb_state"))
+
+
+def test_prototypes_follow_the_header_rules():
+    """Spot checks of each mapping rule of locator_amd/_abi.py on real entry points."""
+    vp, S = C.c_void_p, _lib.SIGNATURES
+    assert S is _abi.PROTOTYPES and len(S) == 89
+    assert S["loc_last_error"] == (C.c_char_p, []) and S["loc_version"] == (C.c_int, [])
+    assert S["loc_make_dims"] == (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_lib.Dims)])
+    assert S["loc_workspace_bn4"] == (vp, [C.POINTER(_lib.Net)])                      # float* return: a device pointer
+    assert S["loc_bn_var_add"] == (C.c_float, [C.c_int])
+    assert S["loc_init_uniform"] == (C.c_int, [vp, C.c_int64, C.c_float, C.c_uint64, C.c_uint64, vp])
+    assert S["loc_kde_peak_batch"] == (C.c_int, [vp, vp, C.c_int, C.c_double, vp, vp, vp])
+    assert S["loc_event_create"] == (C.c_int, [C.POINTER(vp)])                        # T**
+    assert S["loc_event_elapsed_ms"] == (C.c_int, [vp, vp, C.POINTER(C.c_float)])     # h_ms
+    assert S["loc_l1_forward_gemm_i8_partial"][1][-4:] == [C.POINTER(_lib.Tuning), C.POINTER(C.c_int), C.POINTER(vp), vp]
+    assert S["loc_snapshot_if"] == (C.c_int, [vp, vp, vp, C.c_int64, vp])             # loc_cb_state*: a device pointer
+    assert S["loc_stack_dw_adam_tail"][1][-2:] == [vp, vp] and len(S["loc_stack_dw_adam_tail"][1]) == 28
+    assert [len(S[n][1]) for n in ("loc_l1_backward_adam", "loc_l1_backward_adam_chain")] == [31, 32]
+
+
+@pytest.mark.parametrize("text", [
+    "int loc_f(size_t n);",                                    # a scalar type outside the table
+    "typedef struct loc_s { long n; } loc_s;",                 # ... in a struct
+    "int loc_f(int n, const float*);",                         # a parameter without a name
+    "int loc_f(int);",
+    "int loc_f(loc_dims d);",                                  # a struct by value
+    "int loc_f(int n) int loc_g(int n);",                      # two declarations before one `;`
+    "static const int x = 3;",                                 # not a prototype
+    "#define LOC_N (1 << 4)\n",                                # an object-like constant that is not a literal
+])
+def test_parser_refuses_what_it_cannot_type(text):
+    head = "typedef struct loc_dims { int K, Kp; } loc_dims;\n"
+    assert list(_abi.parse(head + "int loc_f(const loc_dims* d, float* h_out);")[2]) == ["loc_f"]
+    with pytest.raises(ValueError):
+        _abi.parse(head + text)
+
+
+def test_constants_come_from_the_header():
+    assert len(_abi.CONSTANTS) == 14 and all(getattr(_abi, k) == v for k, v in _abi.CONSTANTS.items())
+    assert _abi.LOC_PREDICT_CHUNK == 16384 and type(_abi.LOC_PREDICT_CHUNK) is int
+    assert _abi.LOC_DOSAGE_UNIT == 63 == genotypes.DOSAGE_UNIT
+    assert (_abi.LOC_ROWS, _abi.LOC_MAX_WIDTH, _abi.LOC_MAX_BATCH, _abi.LOC_BIG_BATCH_MAX, _abi.LOC_BATCH_SLOT) == (32, 1024, 128, 4096, 128)
+    assert (_abi.LOC_ROWS_TILE, _abi.LOC_ROWS_BLOCKS, _abi.LOC_MAX_FWD_GRID, _abi.LOC_GEMM_I8_PACKED_MIN_ROWS) == (128, 256, 512, 3072)
+    assert (_abi.LOC_GUARD_FAST_MEDIAN, _abi.LOC_GUARD_FAST_MAX, _abi.LOC_GUARD_EXACT_MAX) == (64.0, 512.0, 512.0)
+    lib = _lib.load()
+    assert [lib.loc_gemm_min_rows(p) for p in (1, 2, 3)] == [640, 768, 1152]
+    assert [lib.loc_gemm_i8_min_rows(g) for g in (2, 3)] == [512, 512]
+    for width in (32, 256, 1024):
+        d = _lib.make_dims(1000, width, 4)
+        assert lib.loc_l1_partial_floats(C.byref(d)) == 256 * 128 * d.Hp == max(512 * 32, 256 * 128) * width
+
+
+def test_header_modules_do_not_import_torch(repo_root):
+    """The command line and the fork server start without torch: _abi, genotypes and locator must not pull it in."""
+    code = ("import sys; import locator_amd._abi, locator_amd.genotypes, locator_amd.locator; "
+            "assert 'torch' not in sys.modules, 'torch was imported'")
+    subprocess.check_call([sys.executable, "-c", code], cwd=repo_root)
+
+
+def test_missing_header_is_an_error_that_names_the_path(repo_root, tmp_path):
+    pkg = tmp_path / "locator_amd"
+    pkg.mkdir()
+    (pkg / "__init__.py").write_text("")
+    (pkg / "_abi.py").write_text(open(os.path.join(repo_root, "locator_amd", "_abi.py")).read())
+    r = subprocess.run([sys.executable, "-c", "import locator_amd._abi"], cwd=tmp_path, capture_output=True, text=True)
+    assert r.returncode != 0 and os.path.join(str(tmp_path), "include", "locator_hip.h") in r.stderr
 
 
 def test_dims_and_layout():

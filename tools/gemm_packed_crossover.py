@@ -42,7 +42,7 @@ def main():
     bn4 = torch.zeros(4 * d.Kp, device=dev)
     _lib.check(lib.loc_bn_infer_scale_shift(d.K, d.Kp, P + 4 * lay.gamma, P + 4 * lay.beta, P + 4 * lay.mov_mean,
                                             P + 4 * lay.mov_var, bn4.data_ptr(), st()))
-    partial = torch.empty(256 * 128 * d.Hp, device=dev)
+    partial = torch.empty(lib.loc_l1_partial_floats(C.byref(d)), device=dev)
     image = torch.empty(lib.loc_l1_image_i8_bytes(C.byref(d), a.digits), dtype=torch.uint8, device=dev)
     _lib.check(lib.loc_l1_image_i8_build(C.byref(d), bn4.data_ptr(), P + 4 * lay.w1, a.digits, image.data_ptr(), st()))
     xd = distinct_rows(dev, d.Kp, 16384)

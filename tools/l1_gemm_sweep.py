@@ -148,7 +148,7 @@ def l1_gemm_roofline(net, n_matrix, iters=20, x_distinct=None):
     bn4 = torch.zeros(4 * d.Kp, device=dev)
     _lib.check(lib.loc_bn_infer_scale_shift(d.K, d.Kp, P + 4 * lay.gamma, P + 4 * lay.beta, P + 4 * lay.mov_mean,
                                             P + 4 * lay.mov_var, bn4.data_ptr(), st()))
-    partial = torch.empty(256 * 128 * d.Hp, device=dev)
+    partial = torch.empty(lib.loc_l1_partial_floats(C.byref(d)), device=dev)
 
     def shape(X, n_rows, n_src, in_loop=True):
         rows = (torch.arange(n_rows, dtype=torch.int32, device=dev) % n_src).contiguous()
