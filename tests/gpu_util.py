@@ -58,6 +58,99 @@ def params_err(pa, pb):
     return out
 
 
+# ---------------------------------------------------------------- Adam moments against the oracle (tests/test_gpu_moments.py)
+# Adam divides the gradient by its own running magnitude, so the weights after Adam hardly see a gradient that is off by
+# a constant factor; the moments hold the magnitude itself (m = 0.1 g, v = 0.001 g^2 after the first step).
+
+MOMENT_TILE = 32
+
+
+def tile_norms(a, tile=MOMENT_TILE):
+    """L2 norm (float64) of every tile x tile tile of the 2-D array a: row and column tiles from index 0, edge tiles
+    partial.  -> [ceil(rows / tile), ceil(cols / tile)]"""
+    a = np.asarray(a, np.float64)
+    r, c = a.shape
+    nr, nc = -(-r // tile), -(-c // tile)
+    sq = np.zeros((nr * tile, nc * tile))
+    sq[:r, :c] = a * a
+    return np.sqrt(sq.reshape(nr, tile, nc, tile).sum(axis=(1, 3)))
+
+
+def _rel(num, den):
+    """num / den elementwise; where the reference norm den is 0 the other side has to be exactly 0 as well (-> 0, else
+    inf)."""
+    num, den = np.asarray(num, np.float64), np.asarray(den, np.float64)
+    return np.where(den > 0, num / np.where(den > 0, den, 1.0), np.where(num == 0, 0.0, np.inf))
+
+
+def moments_err(got, ref):
+    """Two dicts in the export_adam() / O.zeros_like_trainable format (one moment each) ->
+    per tensor: {"gamma", "beta", "W<l>", "b<l>"} -> ||got - ref||_2 / ||ref||_2 in float64;
+    per tile:   {"W<l>"} -> the worst value of the same ratio over the 32 x 32 tiles of W[l] (a tensor-wide norm would
+                dilute a wrong k-tile or unit tile at the end of K or H)."""
+    f64 = lambda a: np.asarray(a, np.float64)
+    named = [("gamma", got["gamma"], ref["gamma"]), ("beta", got["beta"], ref["beta"])]
+    for l in range(len(ref["W"])):
+        named += [(f"W{l}", got["W"][l], ref["W"][l]), (f"b{l}", got["b"][l], ref["b"][l])]
+    per_tensor, per_tile = {}, {}
+    for name, g, r in named:
+        assert np.shape(g) == np.shape(r), (name, np.shape(g), np.shape(r))
+        per_tensor[name] = float(_rel(np.linalg.norm(f64(g) - f64(r)), np.linalg.norm(f64(r))))
+        if name[0] == "W":
+            per_tile[name] = float(_rel(tile_norms(f64(g) - f64(r)), tile_norms(r)).max())
+    return per_tensor, per_tile
+
+
+def replay_epoch(p, x, y, rows, batch, masks, drop_p, dtype=np.float64, grad_hook=None):
+    """One epoch of O.train_step (Adam t = 1.., lr 1e-3, moments from zero) in `dtype` on the minibatches
+    rows[j * batch:(j + 1) * batch] with the keep masks masks[j] ([rows of the step or more][mask width or more]).
+    grad_hook(g) may edit the gradients before Adam sees them (the sensitivity tests of tests/test_oracle.py).
+    -> per-step losses, m, v; p itself is left alone."""
+    pr = O.cast_params(p, dtype)
+    m, v = O.zeros_like_trainable(pr), O.zeros_like_trainable(pr)
+    nl = len(pr["W"]) - 2
+    mw = pr["W"][0].shape[0] if O.n_pre(nl) == 0 else pr["W"][0].shape[1]
+    losses = []
+    for j, i in enumerate(range(0, len(rows), batch)):
+        r = rows[i:i + batch]
+        mask = masks[j][:len(r), :mw] if drop_p > 0 else None
+        loss, g, _ = O.loss_and_grads(pr, x[r], y[r], mask, drop_p)
+        if grad_hook is not None:
+            grad_hook(g)
+        O.adam_apply(pr, g, m, v, j + 1, dtype(1e-3))
+        losses.append(float(loss))
+    return np.array(losses), m, v
+
+
+def moments_padding(net, flat):
+    """Entries of the flat adam_m / adam_v buffer that belong to no trainable value: W1 rows K..Kp and units H..Hp (W1S
+    layout), gamma / beta beyond K, b1 / hidden biases beyond H, hidden rows and columns H..Hp, head rows H..Hp and the
+    alignment tail.  -> the values found there (all of them have to be 0)."""
+    d, lay = net.d, net.lay
+    K, Kp, H, Hp, L = d.K, d.Kp, d.H, d.Hp, d.L
+    flat = flat.cpu().numpy()
+    assert flat.size == lay.n_trainable
+    real = np.zeros(flat.size, bool)
+    idx = _w1s_tile_index(Hp)                                         # [32, Hp] offsets inside one k-tile's run
+    for kt in range(Kp // 32):
+        ok = ((32 * kt + np.arange(32))[:, None] < K) & (np.arange(Hp)[None, :] < H)
+        real[lay.w1 + kt * 32 * Hp + idx[ok]] = True
+    real[lay.gamma:lay.gamma + K] = True
+    real[lay.beta:lay.beta + K] = True
+    real[lay.b1:lay.b1 + H] = True
+    sq = np.zeros((Hp, Hp), bool)
+    sq[:H, :H] = True
+    for i in range(L - 1):
+        real[lay.wh + i * Hp * Hp:lay.wh + (i + 1) * Hp * Hp] = sq.reshape(-1)
+        real[lay.bh + i * Hp:lay.bh + i * Hp + H] = True
+    real[lay.wa:lay.wa + 2 * H] = True                                # [Hp][2]: rows H..Hp are padding
+    real[lay.ba:lay.ba + 2] = True
+    real[lay.wb:lay.wb + 4] = True
+    real[lay.bb:lay.bb + 2] = True
+    assert real.sum() == K * H + 2 * K + H + (L - 1) * (H * H + H) + 2 * H + 2 + 4 + 2
+    return flat[~real]
+
+
 # ---------------------------------------------------------------- sparse-support problems (tests/test_gpu_large_k.py)
 # Only a few 32-SNP k-tiles carry real genotypes and keep their first-layer weights; every other SNP column is constant
 # over the samples (mostly 0, one tile of 1s and one of 2s) and its W1 row is zero.  There x - mean = 0 exactly, so those

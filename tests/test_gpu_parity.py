@@ -184,6 +184,9 @@ def test_one_training_step_matches_oracle(K, width, nlayers, n_b, drop_p):
     assert max(params_err(gm, m).values()) < 1e-6
     for l in range(len(p["W"])):
         assert np.allclose(gv["W"][l], v["W"][l], rtol=2e-3, atol=1e-12), l
+        assert np.allclose(gv["b"][l], v["b"][l], rtol=2e-3, atol=1e-12), l
+    assert np.allclose(gv["gamma"], v["gamma"], rtol=2e-3, atol=1e-12)
+    assert np.allclose(gv["beta"], v["beta"], rtol=2e-3, atol=1e-12)
     # padding stays zero
     flat = net.params.cpu().numpy()
     w1 = flat[net.lay.w1:net.lay.w1 + net.d.Hp * net.d.Kp]

@@ -263,3 +263,76 @@ def test_sparse_support_problem_trains_like_its_reduced_problem():
     assert np.abs(p["mov_mean"][inactive] - c[inactive] * (1 - 0.99 ** 9)).max() < 1e-12
     assert np.abs(p["mov_var"][inactive] - 0.99 ** 9).max() < 1e-12
     assert np.abs(O.predict(p, x) - O.predict(pr, x[:, cols])).max() < 1e-12
+
+
+# ---------------------------------------------------------------- Adam moments as an observer of gradient magnitude
+# tests/test_gpu_moments.py compares the device's Adam moments with the oracle's after one epoch.  Here, without a GPU:
+# the metric it uses (tests/gpu_util.moments_err) sees a 10 % error in one gradient tensor at full size, and the fp32
+# oracle's own distance from the float64 one (the floor the GPU bars are multiples of) is four orders of magnitude lower.
+_MOMENT_CASES = [(300, 64, 4, 200, 450), (900, 256, 4, 128, 300)]     # K, width, nlayers, batch, n_train
+_moment_runs = {}
+
+
+def _moment_case(case):
+    """One epoch on `case`, three times: float64, float64 with the layer-1 kernel gradient scaled by 0.9, float32.
+    Computed once per case."""
+    if case not in _moment_runs:
+        from tests.gpu_util import make_problem, replay_epoch
+        K, width, nlayers, batch, n_train = case
+        x, y, p, rng = make_problem(n_train, K, width, nlayers, seed=K + width)
+        perm = rng.permutation(n_train)
+        steps = -(-n_train // batch)
+        masks = (rng.random((steps, batch, width)) >= 0.25).astype(np.uint8)
+
+        def scale_w1(g):
+            g["W"][0] *= 0.9
+        kw = dict(x=x, y=y, rows=perm, batch=batch, masks=masks, drop_p=0.25)
+        _moment_runs[case] = (replay_epoch(p, **kw), replay_epoch(p, grad_hook=scale_w1, **kw),
+                              replay_epoch(p, dtype=np.float32, **kw))
+    return _moment_runs[case]
+
+
+def test_moments_err_on_known_arrays():
+    from tests.gpu_util import moments_err, tile_norms
+    rng = np.random.default_rng(0)
+    ref = {"gamma": rng.normal(size=70), "beta": rng.normal(size=70),
+           "W": [rng.normal(size=(70, 40)), rng.normal(size=(40, 2))], "b": [rng.normal(size=40), np.zeros(2)]}
+    assert tile_norms(ref["W"][0]).shape == (3, 2) and tile_norms(ref["W"][1]).shape == (2, 1)
+    assert np.isclose(tile_norms(ref["W"][0])[2, 1], np.linalg.norm(ref["W"][0][64:, 32:]))
+    assert np.isclose(np.linalg.norm(tile_norms(ref["W"][0])), np.linalg.norm(ref["W"][0]))
+    got = O.copy_params(ref)
+    t, tt = moments_err(got, ref)
+    assert set(t) == {"gamma", "beta", "W0", "b0", "W1", "b1"} and set(tt) == {"W0", "W1"}
+    assert not any(t.values()) and not any(tt.values())          # b1: reference norm 0 and exactly 0 on the other side
+    got["W"][0][64:, 32:] *= 1.5                                  # the last, partial tile (6 x 8 of 70 x 40) alone
+    got["gamma"] *= 0.8
+    got["b"][1][1] = 1e-30
+    t, tt = moments_err(got, ref)
+    assert np.isclose(tt["W0"], 0.5) and 0 < t["W0"] < 0.1 and tt["W1"] == 0
+    assert np.isclose(t["gamma"], 0.2) and t["beta"] == 0 and t["b1"] == np.inf
+
+
+@pytest.mark.parametrize("case", _MOMENT_CASES)
+def test_moments_see_a_ten_percent_gradient_error(case):
+    """g["W"][0] *= 0.9 in every step of one epoch: after it m["W"][0] is off by a relative 0.1 and v["W"][0] by 0.19
+    (the weights move as well, so not to the last digit), where three epochs of weights after Adam move by 3e-5."""
+    from tests.gpu_util import moments_err
+    (_, m, v), (_, mb, vb), _ = _moment_case(case)
+    em, _ = moments_err(mb, m)
+    ev, tv = moments_err(vb, v)
+    assert 0.09 <= em["W0"] < 0.11, em
+    assert 0.17 <= ev["W0"] < 0.21, ev
+    assert tv["W0"] >= 0.17, tv
+
+
+@pytest.mark.parametrize("case", _MOMENT_CASES)
+def test_fp32_oracle_moments_floor(case):
+    """The fp32 NumPy oracle against the float64 one after one epoch: below 1e-4 per tensor and per 32 x 32 tile, on
+    both moments and every step's loss within 2e-5."""
+    from tests.gpu_util import moments_err
+    (l64, m, v), _, (l32, m32, v32) = _moment_case(case)
+    assert np.abs(l64 - l32).max() < 2e-5
+    for got, ref in ((m32, m), (v32, v)):
+        t, tt = moments_err(got, ref)
+        assert max(t.values()) < 1e-4, t
+        assert max(tt.values()) < 1e-4, tt
