@@ -23,6 +23,20 @@
  *     / processes on different streams or devices; safe to capture into a hipGraph.
  *   - return value: 0 = ok, otherwise a hipError_t (or -1 for a bad argument);
  *     loc_last_error() returns a thread-local message.
+ *   - scratch holds nothing between calls.  From loc_net.ws, ws_predict and l1_image and from the scratch a caller
+ *     passes in (partial, gb_scratch, acts, adrop, dz, head_out) a call reads only what the same call wrote, so the
+ *     buffers may come uninitialised and may hold anything - NaN, another fit's bytes - when a call begins.  The
+ *     exceptions are the documented hand-overs: bn4 with bn_ready; the chained layer-1 partial sums and bn4 with
+ *     fwd_done (loc_train_step_chain); l1_image with l1_image_ready / l1_scan_ready.  Inputs that live in the same
+ *     buffers - a1_in of loc_stack_forward_backward (slot 0 of acts), and adrop where it is an input (Dropout right
+ *     after layer 1) - must be finite in EVERY row of the 32-row blocks in use, not only in rows < n_b: the kernels
+ *     carry whole blocks, give the rows >= n_b a loss gradient of exactly 0 and leave dz = 0 there, which the row
+ *     reductions (loc_stack_dw_adam*, the layer-1 backward) rely on.  Nothing outside the documented extents is
+ *     written: not a neighbouring region of the workspace, not a byte past loc_workspace_floats_batch /
+ *     loc_l1_image_bytes / loc_l1_image_i8_bytes, and by loc_stack_forward_backward not the rows of acts, adrop, dz
+ *     and head_out beyond the 32-row blocks in use (nor slot 0 of acts, nor adrop where it is an input or unused).
+ *     tests/test_gpu_scratch.py (every training schedule and predict route on poisoned, guard-banded scratch of
+ *     exactly those sizes) and tests/test_gpu_stack_train.py (the fused training stack, per element) check this.
  *
  * Data layout
  *   X      genotypes, uint8, sample-major [n_samples][x_pitch], x_pitch = Kp.

@@ -58,6 +58,118 @@ def params_err(pa, pb):
     return out
 
 
+# ---------------------------------------------------------------- poisoned scratch and guard bands
+# (tests/test_gpu_scratch.py, tests/test_gpu_stack_train.py; the contract is stated in include/locator_hip.h, Conventions)
+# Scratch comes from torch.empty: in the test processes it is almost always zero or small finite leftovers, in a replicate
+# run it holds the previous fit's bytes.  A read of a slot the same call never wrote, or a store one tile past a region, is
+# invisible on clean buffers; these helpers make both visible without a sanitizer.
+
+GUARD_BYTES = (0xE1, 0xC3, 0xA5, 0x7F)     # little-endian 0x7FA5C3E1: a NaN with a payload no arithmetic produces
+
+
+def poison(t, kind, seed=0):
+    """Fill the contiguous tensor t in place.  "nan": every 32-bit word 0xFFFFFFFF (every byte 0xFF for uint8) - a NaN as
+    fp32, -1 as int32.  "junk": seeded uniform values in +-1e4 (uint8: seeded random bytes) - NaN disappears in fmaxf,
+    `x > 0 ? :` and max-reductions, finite junk does not.  "zero": the clean buffer the other two are compared with."""
+    assert t.is_contiguous(), "poison() fills contiguous buffers"
+    if kind == "zero":
+        t.zero_()
+    elif kind == "nan":
+        if t.dtype == torch.uint8:
+            t.fill_(0xFF)
+        else:
+            assert t.element_size() == 4, t.dtype
+            t.view(torch.int32).fill_(-1)
+    elif kind == "junk":
+        g = torch.Generator(device=t.device)
+        g.manual_seed(int(seed))
+        if t.dtype == torch.uint8:
+            t.random_(0, 256, generator=g)
+        else:
+            t.uniform_(-1e4, 1e4, generator=g)
+    else:
+        raise ValueError(f"poison kind {kind!r}")
+    return t
+
+
+def guarded(n, dtype=torch.float32, margin=128 * 256, device="cuda"):
+    """-> (view, check): `view` is n elements of `dtype`, 256-byte aligned, inside a larger allocation with at least `margin`
+    elements of GUARD_BYTES directly below and directly above it (the view itself starts out as the same pattern);
+    check(what) asserts that both margins still hold it.  Use a margin of at least 128 * Hp floats: a 128-row tile is the
+    largest unit any kernel stores at once."""
+    es = torch.empty(0, dtype=dtype).element_size()
+    front = -(-margin * es // 256) * 256
+    body = n * es
+    total = -(-(front + body + margin * es) // 4) * 4
+    raw = torch.tensor(GUARD_BYTES, dtype=torch.uint8, device=device).repeat(total // 4)
+    view = raw[front:front + body].view(dtype)
+    assert view.numel() == n and view.data_ptr() % 256 == 0, (n, view.data_ptr())
+    expect = raw.clone()
+
+    def check(what="buffer"):
+        torch.cuda.synchronize()
+        for side, lo, hi in (("below", 0, front), ("above", front + body, total)):
+            bad = (raw[lo:hi] != expect[lo:hi]).nonzero().flatten()
+            assert bad.numel() == 0, (f"{what}: {bad.numel()} bytes of the guard margin {side} the buffer were overwritten "
+                                      f"(first at byte {int(bad[0]) + lo - front} relative to the buffer of {body} bytes)")
+    return view, check
+
+
+def scratch_buffers(net, runner=None, with_image=True):
+    """The buffers a poisoned run fills: activations, partial sums, statistics, losses and weight images - never rows,
+    permutations, offsets or masks.  runner: also its per-step losses / validation distances, the epoch's batch
+    statistics (both parities under cross-epoch chaining) and the validation predictions."""
+    out = [net.ws]
+    if net.ws_predict is not None:
+        out.append(net.ws_predict)
+    if with_image and net.l1_image is not None:
+        out.append(net.l1_image)
+    if runner is not None:
+        out += [runner.stats, runner.val_yhat] + (list(runner.stats_ep2) if runner.xchain else [runner.stats_ep])
+    return out
+
+
+def poison_scratch(net, runner, kind, seed=0, with_image=True):
+    torch.cuda.synchronize()
+    for i, t in enumerate(scratch_buffers(net, runner, with_image)):
+        poison(t, kind, seed * 16 + i)
+    torch.cuda.synchronize()
+
+
+def swap_scratch(net, runner=None, kind="zero", seed=0):
+    """Replace net.ws, net.ws_predict (when present) and net.l1_image by guarded views of EXACTLY the sizes the library asks
+    for - loc_workspace_floats_batch for the two workspaces, the largest of loc_l1_image_i8_bytes(d, 3 / 2) and
+    loc_l1_image_bytes(d, 3) for the image (none where the width supports no image) - and poison them (and the runner's
+    statistics / loss buffers) with `kind`.  Call it after the EpochRunner exists (set_batch may reallocate ws) and before
+    its first epoch (the captured graph keeps the pointers).  -> the margins' check callables."""
+    import ctypes as C
+    lib, d = net.lib, net.d
+    margin = 128 * d.Hp
+    need = int(lib.loc_workspace_floats_batch(C.byref(d), int(runner.batch) if runner is not None else 32))
+    assert need <= net.ws.numel(), (need, net.ws.numel())
+    checks = []
+
+    def take(n, dtype, name):
+        view, check = guarded(n, dtype, margin * (4 if dtype == torch.uint8 else 1))     # 128 rows of floats either way
+        checks.append(lambda: check(name))
+        return view
+    net.ws = take(need, torch.float32, "ws")
+    if net.ws_predict is not None:
+        net.ws_predict = take(need, torch.float32, "ws_predict")
+    image = max(int(lib.loc_l1_image_i8_bytes(C.byref(d), 3)), int(lib.loc_l1_image_i8_bytes(C.byref(d), 2)),
+                int(lib.loc_l1_image_bytes(C.byref(d), 3)))
+    net.l1_image = take(image, torch.uint8, "l1_image") if image else None
+    net._net = None
+    net.params_changed()
+    poison_scratch(net, runner, kind, seed)
+    return checks
+
+
+def bits(t):
+    """Host copy of a device tensor's raw 32-bit words (NaNs compare by payload, -0.0 differs from 0.0)."""
+    return t.detach().contiguous().view(-1).view(torch.int32).cpu()
+
+
 # ---------------------------------------------------------------- Adam moments against the oracle (tests/test_gpu_moments.py)
 # Adam divides the gradient by its own running magnitude, so the weights after Adam hardly see a gradient that is off by
 # a constant factor; the moments hold the magnitude itself (m = 0.1 g, v = 0.001 g^2 after the first step).
