@@ -250,6 +250,19 @@ int64_t loc_workspace_floats_batch(const loc_dims* d, int batch);
 int64_t loc_l1_partial_floats(const loc_dims* d);
 
 /* ---- utility kernels ---- */
+/* The random streams.  Every random value is one 32-bit word of Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl
+ * increments 0x9E3779B9 / 0xBB67AE85) of philox(ctr_lo, ctr_hi, key): counter words (lo32(ctr_lo), hi32(ctr_lo),
+ * lo32(ctr_hi), hi32(ctr_hi)), key words (lo32(key), hi32(key)), key = seed:
+ *   loc_init_glorot        logical element (r, c) = word 0 of philox(r * C + c, stream_id, seed), whatever the storage layout
+ *   loc_init_uniform       element i = word i % 4 of philox(i / 4, stream_id, seed)
+ *   loc_dropout_mask_fill  element i of ONE stream per seed = word i % 4 of philox(i / 4, 0x6d61736b "mask", seed);
+ *                          mask[j] = element offset + j >= (uint32)((double)p * 2^32) ? 1 : 0   (offset % 4 == 0)
+ * and a uniform value is (2 u - 1) * limit with u = ((float)word + 0.5f) * 2^-32, every step one fp32 operation.
+ * locator_amd/net.py derives stream_id = (replicate << 16) | layer for the kernels of a net and the mask seed
+ * (seed ^ 0x64726F70) + (replicate << 40).  tests/philox_ref.py restates all of this in NumPy (checked against the
+ * published known answers in tests/test_references.py) and tests/test_gpu_random.py holds the device to it bit for bit.
+ * The other kernels of this section - column gather, genotype maximum and 2-bit packing beyond LOC_GRID_Y_MAX rows, the W1
+ * layout conversions, loc_transpose_hidden - are compared with NumPy in tests/test_gpu_util_kernels.py. */
 /* Keras glorot_uniform init of one Dense kernel (locator.py:319-325 [K]): logical R x C (in x out),
  * U(+-sqrt(6/(R+C))) from Philox4x32-10 keyed by (seed, stream_id, r*C+c); stored row-major
  * [Rp][Cp] or (swizzled=1) as W1S with R = SNPs, C = units.  Padding is written as zero. */
@@ -650,7 +663,11 @@ int loc_explain_reduce(const double* partial, int splits, int Ks, int n, double*
  * on_epoch_end calls do, and loc_snapshot_if copies params -> best when that epoch improved val_loss.  With these two in
  * the epoch's stream (or captured graph) the host can enqueue epochs ahead of the device and read the history rows with
  * a lag (locator_amd/train.py); once early stopping has fired the state, the LR and `best` are frozen, so epochs already
- * enqueued behind the stop epoch are harmless and their rows are dropped. */
+ * enqueued behind the stop epoch are harmless and their rows are dropped.
+ * tests/test_gpu_callbacks.py calls the two entry points epoch by epoch on scripted val_loss sequences (ties, NaN / +inf,
+ * patience 0 and 1, more epochs than hist_cap, epochs behind the stop, both 1024-value staging loops past their first
+ * chunk, a captured graph) and compares the whole state, *lr, hist and best with tests/keras_callbacks_ref.py after every
+ * epoch. */
 typedef struct loc_cb_state {
     double ck_best, es_best, rl_best; /* best val_loss seen by each callback                                            */
     float lr;                         /* current learning rate (fp32, as Keras keeps it); mirrored into *lr             */
