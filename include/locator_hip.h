@@ -36,7 +36,8 @@
  *     loc_l1_image_bytes / loc_l1_image_i8_bytes, and by loc_stack_forward_backward not the rows of acts, adrop, dz
  *     and head_out beyond the 32-row blocks in use (nor slot 0 of acts, nor adrop where it is an input or unused).
  *     tests/test_gpu_scratch.py (every training schedule and predict route on poisoned, guard-banded scratch of
- *     exactly those sizes) and tests/test_gpu_stack_train.py (the fused training stack, per element) check this.
+ *     exactly those sizes), tests/test_gpu_stack_train.py (the fused training stack, per element) and
+ *     tests/test_gpu_l1_train.py (BatchNorm statistics and the layer-1 backward, per element) check this.
  *
  * Data layout
  *   X      genotypes, uint8, sample-major [n_samples][x_pitch], x_pitch = Kp.
@@ -421,13 +422,18 @@ int loc_l1_forward_gemm_i8_partial(const uint8_t* X, int64_t x_pitch, int packed
                                    int64_t partial_floats, int target_blocks, const loc_tuning* tune, int* h_groups,
                                    const float** h_cvec8, void* stream);
 /* Fused: dW1 = xhat^T dZ1, dxhat = dZ1 W1^T -> dgamma/dbeta, Adam on W1/gamma/beta/b1.
- * dW1 and dxhat are never written to memory.  gb_scratch: (Kp/32)*128 floats (per-wave partial
- * sums for dgamma/dbeta, combined in a fixed order by a trailing per-SNP kernel).  If bn_next_stats
+ * dW1 and dxhat are never written to memory.  gb_scratch: (Kp/32)*128 floats for every row count (per-wave partial
+ * sums for dgamma/dbeta, combined in a fixed order by a trailing per-SNP kernel; the call reads and writes nothing
+ * beyond them).  If bn_next_stats
  * ([mean|var] of the NEXT minibatch, from loc_bn_epoch_stats) is non-NULL that kernel also writes the next
- * step's [scale|shift|mean|rstd] to bn4_out from the just-updated gamma/beta.  ev_after_main: optional
- * hipEvent_t recorded between the main kernel and the trailing per-SNP kernel (kernel timing).
- * n_b <= 32 rows per weight tile, or up to LOC_MAX_BATCH on the fused-stack widths 64/128/256: every tile then
- * takes the gradient of all ceil(n_b/32) row blocks (dz1 rows [0, 32*ceil(n_b/32))) before its one Adam update. */
+ * step's [scale|shift|mean|rstd] to bn4_out from the just-updated gamma/beta (entries k < K; NULL: bn4_out is untouched).
+ * ev_after_main: optional hipEvent_t recorded between the main kernel and the trailing per-SNP kernel (kernel timing).
+ * Rows: 1 <= n_b <= 32 at every width; up to LOC_BIG_BATCH_MAX on the fused-stack widths that pad to 64 / 128 / 256 -
+ * 33..LOC_MAX_BATCH rows take the gradient of all ceil(n_b/32) row blocks from LDS before a tile's one Adam update, more
+ * rows stream the blocks from L2 (l1_bwd_adam_big_kernel).  Other row counts and widths are refused, nothing written.
+ * dz1: [32*ceil(n_b/32)][Hp] floats, all of them read: rows n_b.. of the last block (and units >= width) must be
+ * exactly 0, as loc_stack_forward_backward leaves them.  rows: n_b entries.  tests/test_gpu_l1_train.py holds every
+ * form to a float64 reference on guarded buffers of exactly these sizes. */
 int loc_l1_backward_adam(const uint8_t* X, int64_t x_pitch, const int32_t* rows, int n_b, const loc_dims* d,
                          const float* bn4, const float* dz1, float* w1s, float* m1s, float* v1s,
                          float* gamma, float* beta, float* m_gamma, float* v_gamma, float* m_beta, float* v_beta,
@@ -437,7 +443,8 @@ int loc_l1_backward_adam(const uint8_t* X, int64_t x_pitch, const int32_t* rows,
                          void* stream);
 
 /* loc_l1_backward_adam for --nlayers 1 (Dropout on the BatchNorm output, see loc_l1_forward_in_dropout): dW1 uses
- * xhat * mask * keep_scale and the gradient reaching gamma / beta is dxhat * mask * keep_scale.  n_b <= 32. */
+ * xhat * mask * keep_scale and the gradient reaching gamma / beta is dxhat * mask * keep_scale.  n_b <= 32; in_mask
+ * [32][Kp] keep flags. */
 int loc_l1_backward_adam_in_dropout(const uint8_t* X, int64_t x_pitch, const int32_t* rows, int n_b, const loc_dims* d,
                                     const float* bn4, const float* dz1, float* w1s, float* m1s, float* v1s,
                                     float* gamma, float* beta, float* m_gamma, float* v_gamma, float* m_beta,

@@ -740,22 +740,23 @@ __global__ __launch_bounds__(RB > 2 ? 512 : 256, RB > 2 ? 1 : 2) void l1_bwd_ada
 // but streams dz from L2 row block by row block: per unit and 32-row block 16 fp32 MFMAs (v_mfma_f32_32x32x2_f32:
 // exact fp32 products) whose A operand is a coalesced 128-byte read of dz and whose B operand is x - c for the
 // block's rows.  It is matrix-bound (2 x n_b MFMA cycles per 12 KB of weight stream), not HBM-bound - a correct path
-// for a setting far from the default, not a tuned one.  dzsum comes from dz_colsum_kernel.  Same work partition, cache
+// for a setting far from the default, not a tuned one.  dzsum comes from dz_colsum (below).  Same work partition, cache
 // policy, gamma/beta hand-off (gbs slots) and Adam arithmetic as the other two kernels.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void dz_colsum_kernel(const float* __restrict__ dz1, int n_rows, int Hp,
-                                                        float* __restrict__ dzsum) {
-    const int h = blockIdx.x * 256 + threadIdx.x;
-    if (h >= Hp) return;
+// dzsum[h] = sum_b dz1[b][h] over the n_rows rows of the row blocks in use, one unit per thread, rows in index order (a
+// fixed order: the sum does not depend on the launch).  Every workgroup of l1_bwd_adam_big_kernel takes its own copy
+// into LDS - dz1 is in L2 after the first - so the sum needs no scratch of its own: gb_scratch keeps the (Kp/32)*128
+// floats of the other forms, whose every float the flushes of a running launch may overwrite at any time.
+__device__ __forceinline__ float dz_colsum(const float* __restrict__ dz1, int n_rows, int Hp, int h) {
     float s = 0.f;
     for (int b = 0; b < n_rows; ++b) s += dz1[(int64_t)b * Hp + h];      // fixed order
-    dzsum[h] = s;
+    return s;
 }
 
 template <int NHT, int NTM>
 __global__ __launch_bounds__(256, 2) void l1_bwd_adam_big_kernel(
     const uint8_t* __restrict__ X, int64_t pitch, const int32_t* __restrict__ rows, int n_b, int K, int Kp,
-    const float* __restrict__ bn4, const float* __restrict__ dz1, const float* __restrict__ dzsum_g,
+    const float* __restrict__ bn4, const float* __restrict__ dz1,
     float* __restrict__ w1s, float* __restrict__ m1s, float* __restrict__ v1s, float* __restrict__ gbs,
     float* __restrict__ b1, float* __restrict__ m_b1, float* __restrict__ v_b1, const float* __restrict__ alpha_tab,
     int alpha_tab_len, const float* __restrict__ lr, const int* __restrict__ t_base, int t_off, int n_active) {
@@ -768,7 +769,7 @@ __global__ __launch_bounds__(256, 2) void l1_bwd_adam_big_kernel(
     const int nkt = Kp / KT;
     const int nrb = (n_b + 31) / 32;                                // dz rows n_b..32*nrb-1 are zero (stack kernel)
     const float alpha = adam_alpha(alpha_tab, alpha_tab_len, lr, t_base, t_off);
-    for (int h = t; h < Hp; h += 256) dzsum[h] = dzsum_g[h];
+    for (int h = t; h < Hp; h += 256) dzsum[h] = dz_colsum(dz1, 32 * nrb, Hp, h);
     for (int i = t; i < 32 * nrb; i += 256) rows_l[i] = i < n_b ? rows[i] : rows[0];
     __syncthreads();
     if (blockIdx.x == 0) {
@@ -1091,17 +1092,12 @@ static int l1_backward_main_impl(const uint8_t* X, int64_t x_pitch, const int32_
     if (n_active > nkt) n_active = nkt;
     grid = (n_active + 3) / 4;
     if (n_b > LOC_MAX_BATCH) {
-        // more than 128 rows: row blocks streamed from L2 (l1_bwd_adam_big_kernel); dzsum goes through the first Hp
-        // floats of gb_scratch's tail, which is free until the kernel's own flushes (they write [0, 4*Kp))
+        // more than 128 rows: row blocks streamed from L2 (l1_bwd_adam_big_kernel)
         if (in_mask) { loc_set_error("loc_l1_backward_adam: --nlayers 1 with dropout needs --batch_size <= 32"); return -1; }
-        float* dzsum = gb_scratch + 4 * (int64_t)d->Kp;
-        hipLaunchKernelGGL(dz_colsum_kernel, dim3((d->Hp + 255) / 256), dim3(256), 0, (hipStream_t)stream, dz1,
-                           (n_b + 31) / 32 * 32, d->Hp, dzsum);
-        LOC_CHECK_LAUNCH();
         const size_t lds_big = ((size_t)d->Hp + (size_t)(n_b + 31) / 32 * 32) * sizeof(float);
 #define LAUNCH_BWD_BIG(N)                                                                                      \
     hipLaunchKernelGGL((l1_bwd_adam_big_kernel<N, 13>), dim3(grid), dim3(256), lds_big, (hipStream_t)stream, X, x_pitch, \
-                       rows, n_b, d->K, d->Kp, bn4, dz1, dzsum, w1s, m1s, v1s, gb_scratch, b1, m_b1, v_b1,     \
+                       rows, n_b, d->K, d->Kp, bn4, dz1, w1s, m1s, v1s, gb_scratch, b1, m_b1, v_b1,            \
                        alpha_tab, alpha_tab_len, lr, t_base, t_off, n_active);
         switch (nht) {
             case 2: LAUNCH_BWD_BIG(2) break;

@@ -59,7 +59,8 @@ def params_err(pa, pb):
 
 
 # ---------------------------------------------------------------- poisoned scratch and guard bands
-# (tests/test_gpu_scratch.py, tests/test_gpu_stack_train.py; the contract is stated in include/locator_hip.h, Conventions)
+# (tests/test_gpu_scratch.py, tests/test_gpu_stack_train.py, tests/test_gpu_l1_train.py; the contract is stated in
+# include/locator_hip.h, Conventions)
 # Scratch comes from torch.empty: in the test processes it is almost always zero or small finite leftovers, in a replicate
 # run it holds the previous fit's bytes.  A read of a slot the same call never wrote, or a store one tile past a region, is
 # invisible on clean buffers; these helpers make both visible without a sanitizer.
@@ -357,3 +358,29 @@ def untouched(section, tiles, value, per_tile, atol=0.0, chunk=1 << 26):
             bad += int(((part != value) if atol == 0 else ((part - value).abs_() > atol)).sum().item())
         start = max(start, end + per_tile)
     return bad
+
+
+def w1s_pack(w_kh, Kp, Hp):
+    """[K][H] (Keras orientation, K <= Kp, H <= Hp) -> the flat W1S array of Kp * Hp fp32 values, padding zero."""
+    w_kh = np.asarray(w_kh, np.float32)
+    full = np.zeros((Kp, Hp), np.float32)
+    full[:w_kh.shape[0], :w_kh.shape[1]] = w_kh
+    idx = _w1s_tile_index(Hp)
+    out = np.empty(Kp * Hp, np.float32)
+    for kt in range(Kp // 32):
+        out[kt * 32 * Hp + idx] = full[32 * kt:32 * kt + 32]
+    return out
+
+
+def w1s_unpack(flat, Kp, Hp):
+    """The inverse: flat W1S array (W1 or one of its Adam moments) -> [Kp][Hp], padding included."""
+    flat = np.asarray(flat)
+    assert flat.size == Kp * Hp, (flat.size, Kp, Hp)
+    idx = _w1s_tile_index(Hp)
+    return np.concatenate([flat[kt * 32 * Hp:(kt + 1) * 32 * Hp][idx] for kt in range(Kp // 32)], 0)
+
+
+def ulp32(a):
+    """Spacing of the fp32 numbers at |a| (float64 array): the unit in which "within n ulp" is counted."""
+    a = np.abs(np.asarray(a, np.float64)).astype(np.float32)
+    return np.spacing(np.maximum(a, np.float32(1.1754944e-38))).astype(np.float64)

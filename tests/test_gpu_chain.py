@@ -285,7 +285,7 @@ def test_chain_kernel_against_the_two_kernels_it_replaces(K, n_b, n_b_next, widt
         tail = [C.c_void_p(net.alpha_tab.data_ptr()), len(net.alpha_tab), C.c_void_p(net.lr_t.data_ptr()),
                 C.c_void_p(net.t_base_t.data_ptr()), 1]
         if which == "pair":
-            gbs = torch.zeros(4 * Kp + Hp, device=dev)
+            gbs = torch.zeros(4 * Kp, device=dev)
             _lib.check(lib.loc_l1_backward_adam(C.c_void_p(net.X.data_ptr()), net.X.stride(0), C.c_void_p(rows.data_ptr()),
                                                 n_b, C.byref(d), C.c_void_p(bn4.data_ptr()), C.c_void_p(dz.data_ptr()),
                                                 *common, C.c_void_p(gbs.data_ptr()), *tail, net.l1_bwd_grid,

@@ -29,6 +29,8 @@ pytestmark = pytest.mark.gpu
     (1000, 256, 6, 256, 600),  # --batch_size 256 at the default width: eight row blocks; last batch of 88
     (500, 128, 4, 300, 700),   # --batch_size 300: ten row blocks (run-time block count past the eight waves); last 100
     (700, 256, 10, 129, 400),  # --batch_size 129: one row past the row-block kernels; last batch of 13
+    (300, 64, 4, 4096, 4200),  # --batch_size 4096, the limit: 128 row blocks per step; last batch of 104
+    (1000, 256, 6, 1024, 2100),  # --batch_size 1024 at the default width: steps of 1024, 1024 and 52 rows
     (300, 600, 3, 32, 70),     # --width 600 (> 512: per-layer kernels, 19 unit tiles, single-buffered layer-1 forward)
     (97, 1024, 2, 16, 40),     # --width 1024, the limit: 32 unit tiles; K = 3 tiles + 1 SNP
     (500, 520, 4, 32, 64),     # --width 520 pads to 544 (17 unit tiles)
@@ -189,6 +191,9 @@ def test_unsupported_configurations_are_rejected_with_messages():
     with pytest.raises(ValueError, match="batch_size"):
         EpochRunner(LocatorNet(X, Y, 40, 64, 4), tr, va, 4097)
     EpochRunner(LocatorNet(X, Y, 40, 64, 4), tr, va, 129)              # above 128 is accepted since round 3
+    with pytest.raises(ValueError, match=r"--batch_size must be in 1\.\.4096 for the HIP path \(got 4097\)"):
+        LocatorNet(X, Y, 40, 64, 4).set_batch(4097)                    # the limit is LOC_BIG_BATCH_MAX, refused by the net itself
+    assert LocatorNet(X, Y, 40, 64, 4).set_batch(4096) == 4096
     with pytest.raises(ValueError, match="batch_size"):
         EpochRunner(LocatorNet(X, Y, 40, 64, 4), tr, va, 0)
     with pytest.raises(ValueError, match="width"):

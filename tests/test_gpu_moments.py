@@ -60,6 +60,9 @@ CASES = [
     (700, 256, 10, 129, 400, None, None, _route_row_blocks(256)),                                    # 129 x 3, 13
     (300, 64, 4, 200, 450, None, None, _route_row_blocks(256)),                                      # 200, 200, 50
     (500, 128, 4, 300, 700, None, None, _route_row_blocks(384)),                                     # 300, 300, 100
+    (400, 128, 4, 1000, 2300, None, None, _route_row_blocks(1024)),                                  # 1000, 1000, 300
+    (300, 64, 4, 1024, 2100, None, None, _route_row_blocks(1024)),                                   # 1024, 1024, 52
+    (500, 256, 4, 4096, 4200, None, None, _route_row_blocks(4096)),                                  # 4096 (the limit), 104
     (300, 64, 1, 32, 70, None, None, _route_in_dropout),                                             # 32, 32, 6
     (97, 33, 1, 7, 30, None, None, _route_in_dropout),                                               # 7 x 4, 2
     (400, 128, 2, 32, 80, None, None, _route_dr(True)),                                              # 32, 32, 16
@@ -72,7 +75,7 @@ CASES = [
 IDS = ["unchained-32", "width256-nt-streams", "width256-l1b-rows", "chain-tail-merged", "chain-tail-own-launch",
        "chain-width128", "chain-width512", "chain-padded-K257-w33", "two-block-chain", "batch33-row-blocks",
        "batch96-row-blocks", "batch100-row-blocks", "batch128-width256", "batch129-big-batch", "batch200-big-batch",
-       "batch300-big-batch", "nlayers1-in-dropout", "nlayers1-K97-batch7", "nlayers2-dropout-after-l1-chained",
+       "batch300-big-batch", "batch1000-big-batch", "batch1024-big-batch", "batch4096-the-limit", "nlayers1-in-dropout", "nlayers1-K97-batch7", "nlayers2-dropout-after-l1-chained",
        "nlayers3-dropout-after-l1-unchained", "width96-per-layer", "width8-K20-per-layer", "width600-per-layer",
        "width1024-per-layer"]
 
