@@ -7,9 +7,15 @@
 // backward, with no communication between workgroups at all.  Every workgroup streams each layer's
 // 256 KB kernel from L2 (coalesced 16-byte loads; the backward pass reads a transposed copy kept in
 // sync by the Adam kernel), contracting on the vector ALU (R rows is far below an MFMA tile).  The
+// stream is a register ring of untracked asm loads with hand-counted waits (round 7): a slot of rows is
+// requested again the moment it has been consumed, across layer boundaries, so that a layer's worth of
+// requests stays in flight through the reduction, the barriers and the epilogue of every pass; the
+// compiler's own counting put a full drain in front of every backward pass.  The
 // row-reducing work — dW, db and Adam for all hidden layers and the heads, and the batch loss — runs
 // afterwards in ONE wide launch (stack_dw_all_kernel), one workgroup per 32x32 weight tile.
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "common.h"
 #include "stack_tail.h"
@@ -23,6 +29,74 @@
 // stack_fused_kernel no thread ever reads another thread's GLOBAL writes, so LDS ordering is all the
 // barrier has to provide ("memory" keeps the compiler from moving accesses across it).
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// Untracked loads of a worker (the compiler neither counts nor waits for them; sf_wait does).
+// 16 bytes at (wave-uniform base) + (the lane's 32-bit byte offset) + OFF.  The destination is a fresh definition ("=v").
+// That a ring register is never copied while its load is in flight follows from how the requests are placed, not from the
+// constraint: every request is unconditional (one chain of definitions per register, nothing for the compiler to merge),
+// and the readers of the old rows are ordered in front of the request (trip(): the sums pass through an asm statement),
+// so the old value is dead where the new one is defined and both get the same register.  The ISA of every instantiation
+// shows no move of a ring register; look again after any change here.
+template <int OFF>
+__device__ __forceinline__ void sf_gload16(f32x4& v, const void* base, uint32_t voff) {
+    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(v) : "v"(voff), "s"(base), "n"(OFF) : "memory");
+}
+// the base of such a request must be in scalar registers: a pointer that is the same in every lane, said so to the compiler
+__device__ __forceinline__ const float* sf_uniform(const float* p) {
+    const uint64_t u = reinterpret_cast<uint64_t>(p);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
+    return reinterpret_cast<const float*>(((uint64_t)hi << 32) | lo);
+}
+// 4 bytes / 1 byte (zero-extended) at a per-lane address.  Several of these sit behind a condition, so the destination is an
+// in-out operand ("+v") of an initialised variable: the load overwrites the register that holds the initial value, and there
+// is no second value that a merge behind the condition could make the compiler copy while the load is in flight.
+template <class T>
+__device__ __forceinline__ void sf_gload4(T& v, const void* p) {
+    static_assert(sizeof(T) == 4, "one register");
+    asm volatile("global_load_dword %0, %1, off" : "+v"(v) : "v"(p) : "memory");
+}
+__device__ __forceinline__ void sf_gload1(uint32_t& v, const void* p) {
+    asm volatile("global_load_ubyte %0, %1, off" : "+v"(v) : "v"(p) : "memory");
+}
+// Wait until at most N vector-memory operations of the wave are outstanding.  COUNTING RULE (one counter for loads and
+// stores): loads land in order among loads, but a store may retire before an older load.  So "at most N outstanding"
+// proves that a load has landed only if N is the number of LOADS that EVERY wave issues after it: stores never count,
+// and neither do loads behind a condition.  sf_landed(x) right behind the wait ties a register that the wait protects:
+// asm volatile statements keep their order, and every use of x depends on the tie, so none can be scheduled above the
+// wait.  (-DLOC_STACK_DEBUG_DRAIN, `make debug_drain`: every hand count becomes vmcnt(0); tests compare the two builds
+// bit for bit.)
+#ifdef LOC_STACK_DEBUG_DRAIN
+#define SF_VMCNT(N) 0
+#else
+#define SF_VMCNT(N) (N)
+#endif
+template <int N>
+__device__ __forceinline__ void sf_wait() {
+    static_assert(N >= 0 && N <= 63, "vmcnt has six bits");
+    asm volatile("s_waitcnt vmcnt(%0)" : : "n"(SF_VMCNT(N)) : "memory");
+}
+template <class T>
+__device__ __forceinline__ void sf_landed(T& x) { asm volatile("" : "+v"(x)); }
+
+// e0^2 + e1^2 of the loss, with its roundings written out.  Left to the compiler, which product is fused into the sum is its
+// choice per instantiation, and it changes with unrelated code around it (a distance then moves by an ulp and val_loss with it).
+// These are the forms the kernels have had since round 1: the training launch rounds both products and adds them, the eval
+// launch rounds e0^2 and fuses e1^2 into the sum.
+__device__ __forceinline__ float sf_sumsq_train(float e0, float e1) {
+#pragma clang fp contract(off)
+    const float a = e0 * e0, b = e1 * e1;
+    return b + a;
+}
+__device__ __forceinline__ float sf_sumsq_eval(float e0, float e1) { return fmaf(e1, e1, e0 * e0); }
+// the wait in front of a ring slot, with the slot's registers tied to it
+template <int N>
+__device__ __forceinline__ void sf_wait_slot(f32x4& a) {
+    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(a) : "n"(SF_VMCNT(N)) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void sf_wait_slot(f32x4& a, f32x4& b, f32x4& c, f32x4& d) {
+    asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(SF_VMCNT(N)) : "memory");
+}
 
 template <int NHT, int R, bool TRAIN>
 __global__ __launch_bounds__(SF_THREADS) void stack_fused_kernel(
@@ -78,12 +152,138 @@ __global__ __launch_bounds__(SF_THREADS) void stack_fused_kernel(
     const int r0 = li * R;
     const int64_t blk = (int64_t)slot_rows * Hp, HH = (int64_t)Hp * Hp;      // slot = activations of one layer
 
+    // out[r][n] = sum_k in[r][k] * Wcur[k][n]: partial over this thread's k-group, reduced over groups later.
+    // The weight stream runs through a register ring: RING rows of the thread's k-group (32 f32x4 at widths 256 and 512, the
+    // whole k-group below that) cut into NS slots of RW rows.  A slot is requested again the moment its rows have been
+    // consumed, for the chunk one ring length ahead; past the end of a layer that is the NEXT pass's kernel.  So a ring's
+    // worth of rows (a whole layer per workgroup up to width 256, 256 KB at width 512) is in flight at all times, across the
+    // reduction, the barriers and the epilogue too.  A pass is KPG / RW chunks = a whole number of trips round the ring:
+    // every pass starts at slot 0 and the registers are indexed statically while L stays a run-time value.  Every thread
+    // still adds its k ascending, so the sums are what they were.
+    //
+    // From the first ring request to the last epilogue every load of a worker is an untracked asm load and every wait is
+    // counted by hand (the rule is above sf_wait): a load the compiler tracks would be waited for with the ring's younger
+    // requests, i.e. by draining the ring.  Stores stay plain: nothing waits for them.
+    constexpr int RING = KPG < 32 ? KPG : 32;
+    constexpr int RW = RING >= 16 ? RING / 8 : 1;      // rows per slot: 4 at widths 256 / 512, 1 at 128 (8 slots) and 64 (2)
+    constexpr int NS = RING / RW, NTRIP = KPG / RING;
+    constexpr int ROWB = C4 * 16;                      // bytes of a weight row
+    static_assert(KPG >= 2 && NS >= 2 && NS * RW == RING && NTRIP * RING == KPG, "a pass must be whole trips round the ring");
+    static_assert(ROWB <= 4096 && (RW == 1 || 4096 % ROWB == 0), "row offsets are split into a register part and an immediate");
+    // per-thread output slots of the epilogues: element i = t + SF_THREADS*o of the R x Hp block.  Threads past the block
+    // (R * Hp < SF_THREADS) request element i % (R * Hp) and drop it: the loads that a wait counts are never conditional.
+    constexpr int NO = (R * Hp + SF_THREADS - 1) / SF_THREADS;
+    static_assert((R * Hp) % SF_THREADS == 0 || R * Hp < SF_THREADS, "epilogue slots");
+    f32x4 ring[RING];
+    // a request is (uniform matrix + chunk) + (the thread's own 32-bit byte offset, < 4 * Hp * Hp) + (row in the slot).
+    // The instruction's immediate reaches 4095 bytes; rows of a slot beyond that use the offset register + 4096 * n.
+    constexpr int NOFF = (RW * ROWB + 4095) / 4096;
+    uint32_t toff[NOFF];
+#pragma unroll
+    for (int n = 0; n < NOFF; ++n) toff[n] = ((uint32_t)(kq * KPG) * C4 + c4) * 16u + 4096u * n;
+    auto load_slot = [&](const float* __restrict__ Wsrc, int c, int s) {
+        const char* base = reinterpret_cast<const char*>(Wsrc) + (size_t)c * (RW * ROWB);
+        static_assert(RW == 1 || RW == 4, "rows per slot");
+        sf_gload16<0>(ring[s * RW], base, toff[0]);
+        if constexpr (RW == 4) {
+            sf_gload16<ROWB % 4096>(ring[s * RW + 1], base, toff[ROWB / 4096]);
+            sf_gload16<(2 * ROWB) % 4096>(ring[s * RW + 2], base, toff[2 * ROWB / 4096]);
+            sf_gload16<(3 * ROWB) % 4096>(ring[s * RW + 3], base, toff[3 * ROWB / 4096]);
+        }
+    };
+    auto fma_slot = [&](int c, int s, f32x4 (&acc)[R]) {
+#pragma unroll
+        for (int j = 0; j < RW; ++j) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const float a = act[r][kq * KPG + c * RW + j];
+                acc[r][0] = fmaf(a, ring[s * RW + j][0], acc[r][0]);
+                acc[r][1] = fmaf(a, ring[s * RW + j][1], acc[r][1]);
+                acc[r][2] = fmaf(a, ring[s * RW + j][2], acc[r][2]);
+                acc[r][3] = fmaf(a, ring[s * RW + j][3], acc[r][3]);
+            }
+        }
+    };
+    // One trip round the ring: chunks c0 .. c0 + NS - 1 of the matrix in the ring are consumed and slot s is requested
+    // again for chunk cn + s of Wn, never behind a condition: a register with one chain of definitions stays one register,
+    // while a conditional request would have the compiler copy ring registers whose loads are still in flight.  The wait in front of slot s: it was requested one trip ago, and younger than
+    // it are the NS - 1 other slots (RW loads each) and, in the LAST trip of a pass, the pass's NO epilogue operands, which
+    // are requested right in front of that trip (younger loads that only some waves issue are not counted: they make the
+    // wait longer, never shorter).
+    auto trip = [&](auto last, int c0, const float* __restrict__ Wn, int cn, f32x4 (&acc)[R]) {
+        constexpr int N = (NS - 1) * RW + (decltype(last)::value ? NO : 0);
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            if constexpr (RW == 4) sf_wait_slot<N>(ring[s * RW], ring[s * RW + 1], ring[s * RW + 2], ring[s * RW + 3]);
+            else sf_wait_slot<N>(ring[s * RW]);
+            fma_slot(c0 + s, s, acc);
+            // the slot's last use comes before its request: the sums pass through an asm statement in front of it, or the
+            // compiler would let the FMAs trail the request and keep the old rows in a copy taken before they landed
+#pragma unroll
+            for (int r = 0; r < R; ++r) sf_landed(acc[r]);
+            load_slot(Wn, cn + s, s);
+        }
+    };
+    // On entry the first RING rows of Wcur's k-group are in the ring (or in flight).  `operands` requests the epilogue's
+    // operands in front of the last trip, so that exactly RING loads are younger than they are.  The last trip refills the
+    // ring from the next pass's kernel; Wnext is always a valid matrix (see wseq).
+    auto contract = [&](const float* __restrict__ Wcur, const float* __restrict__ Wnext, auto operands) {
+        f32x4 acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+        for (int tr = 0; tr + 1 < NTRIP; ++tr) trip(std::false_type{}, tr * NS, Wcur, (tr + 1) * NS, acc);
+        operands();
+        trip(std::true_type{}, (NTRIP - 1) * NS, Wnext, 0, acc);
+#pragma unroll
+        for (int r = 0; r < R; ++r) *reinterpret_cast<f32x4*>(&part[kq][r][4 * c4]) = acc[r];
+    };
+    // Behind the last pass the ring's requests are dummies that nobody consumes; they may land until the wave ends, so
+    // their registers must not be handed to anything else before: ring_end() keeps them the ring's up to that point.
+    auto ring_end = [&]() {
+        sf_wait<0>();
+#pragma unroll
+        for (int k = 0; k < RING; ++k) sf_landed(ring[k]);
+    };
+    // weight matrix of pass p: forward layers 2..L use Wh[0..L-2]; backward L..2 use WhT[L-2..0]
+    const int n_pass = TRAIN ? 2 * (L - 1) : (L - 1);
+    auto wseq = [&](int p) -> const float* {
+        // The dummy behind the last pass is the first RING rows of every k-group of Wh[0]: rows kq * KPG + j < Hp of the
+        // first hidden kernel, which exists at every width since L >= 2.  Every other request is a row of the matrix of
+        // a pass that runs.  So every address of the stream lies inside Wh or WhT.
+        if (p >= n_pass) return sf_uniform(Wh);
+        return sf_uniform(p < L - 1 ? Wh + (int64_t)p * HH : WhT + (int64_t)(2 * (L - 1) - 1 - p) * HH);
+    };
+    auto ring_start = [&]() {
+        const float* W0 = wseq(0);
+#pragma unroll
+        for (int s = 0; s < NS; ++s) load_slot(W0, s, s);
+    };
+    auto reduced = [&](int r, int n) {     // fixed-order sum over the k-groups
+        float s = 0.f;
+#pragma unroll
+        for (int g = 0; g < KG; ++g) s += part[g][r][n];
+        return s;
+    };
+
+    // head operands: consumed after the forward chain.  The thread count is a multiple of the width, so element
+    // i = t + SF_THREADS*o of the row block is column t % Hp for every o, and one pair of wa per thread serves the heads
+    // (threads t < Hp) and the dz_L phase.
+    static_assert(SF_THREADS % Hp == 0, "one pair of wa per thread needs a thread count that is a multiple of the width");
+    float h_wa0 = 0.f, h_wa1 = 0.f;
+    float h_ba0 = 0.f, h_ba1 = 0.f, h_w00 = 0.f, h_w01 = 0.f, h_w10 = 0.f, h_w11 = 0.f, h_bb0 = 0.f, h_bb1 = 0.f;
+    float h_y0 = 0.f, h_y1 = 0.f;
+    const bool has_y = Y != nullptr && t < R && r0 + t < n_b;
+
     // rows of this block: input of layer 2
     if (!TRAIN && rd_partial != nullptr) {
         // the many-row layer-1 GEMM left its SNP-group partial sums: the group sum + shift term + b1 + ELU that
         // l1_gemm_reduce_kernel would do in a launch of its own (33 MB read back by one kernel at 1000 and at 4096 rows)
         // happens here, spread over every row block of the stack launch.  Same association as that kernel - four
         // quarters of the groups, ((q0 + q1) + q2) + q3, then + (shift + b1) - so the activations are the same bits.
+        // The group count is a run-time value, so these loads cannot all be requested ahead of the ring, and loads return
+        // in order: a ring requested first would be drained by the first partial sum.  They stay the compiler's, in front
+        // of every asm load; the ring starts behind them, in front of the barrier.
         const int gq = (rd_G + 3) / 4;
         for (int i = t; i < R * Hp; i += SF_THREADS) {
             const int r = i / Hp, n = i % Hp;
@@ -105,102 +305,67 @@ __global__ __launch_bounds__(SF_THREADS) void stack_fused_kernel(
             }
             act[r][n] = v;
         }
-    } else {
-        for (int i = t; i < R * Hp; i += SF_THREADS) act[i / Hp][i % Hp] = a1_in[(int64_t)(r0 + i / Hp) * Hp + i % Hp];
     }
-    __syncthreads();
-
-    // out[r][n] = sum_k in[r][k] * Wcur[k][n]: partial over this thread's k-group, reduced over groups later.
-    // The weight stream is software-pipelined: two register buffers of CH rows; while one is consumed
-    // the other is in flight, and the first chunk of the NEXT layer's kernel is requested before this
-    // layer's reduction so L2 latency never sits on the chain.  Chunk 0 of Wcur is already in bufA.
-    constexpr int CH = (KPG / 2) < 16 ? (KPG / 2) : 16;
-    constexpr int NCH = KPG / CH;
-    static_assert(KPG >= 2 && NCH % 2 == 0, "k-group must split into an even number of chunks");
-    f32x4 bufA[CH], bufB[CH];
-    auto load_chunk = [&](const float* __restrict__ Wsrc, int c, f32x4 (&buf)[CH]) {
-        const f32x4* wp = reinterpret_cast<const f32x4*>(Wsrc) + (int64_t)(kq * KPG + c * CH) * C4 + c4;
+    {
+        // Everything the prologue needs is requested first and the ring right behind it: loads return in order, so the wait
+        // in front of the staging covers exactly these and the first, coldest weight fetch runs beside the staging and the
+        // barrier.
+        const bool stage = TRAIN || rd_partial == nullptr;
+        float a1v[NO];
+        uint32_t yrow = 0;
 #pragma unroll
-        for (int j = 0; j < CH; ++j) buf[j] = wp[(int64_t)j * C4];
-    };
-    auto fma_chunk = [&](int c, const f32x4 (&buf)[CH], f32x4 (&acc)[R]) {
-#pragma unroll
-        for (int j = 0; j < CH; ++j) {
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const float a = act[r][kq * KPG + c * CH + j];
-                acc[r][0] = fmaf(a, buf[j][0], acc[r][0]);
-                acc[r][1] = fmaf(a, buf[j][1], acc[r][1]);
-                acc[r][2] = fmaf(a, buf[j][2], acc[r][2]);
-                acc[r][3] = fmaf(a, buf[j][3], acc[r][3]);
-            }
+        for (int o = 0; o < NO; ++o) {
+            const int i = t + SF_THREADS * o;
+            a1v[o] = 0.f;
+            if (stage && i < R * Hp) sf_gload4(a1v[o], a1_in + (int64_t)(r0 + i / Hp) * Hp + i % Hp);
         }
-    };
-    // On entry chunks 0 and 1 of Wcur are in bufA / bufB (or in flight).  Each buffer is refilled with the
-    // chunk two ahead the moment it has been consumed; past the end of this layer that is the NEXT pass's
-    // kernel (Wnext is always a valid matrix: the last pass prefetches a dummy), so ~a whole layer
-    // (256 KB per workgroup) is in flight across the reduction phase and no load is conditional.
-    auto contract = [&](const float* __restrict__ Wcur, const float* __restrict__ Wnext) {
-        f32x4 acc[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-        for (int c = 0; c < NCH; c += 2) {
-            const bool wrap = c + 2 >= NCH;
-            const float* Wn = wrap ? Wnext : Wcur;
-            const int cn = wrap ? c + 2 - NCH : c + 2;
-            fma_chunk(c, bufA, acc);
-            load_chunk(Wn, cn, bufA);
-            fma_chunk(c + 1, bufB, acc);
-            load_chunk(Wn, cn + 1, bufB);
+        if (has_y) sf_gload4(yrow, rows + r0 + t);
+        sf_gload4(h_wa0, wa + 2 * (t % Hp));
+        sf_gload4(h_wa1, wa + 2 * (t % Hp) + 1);
+        if (t < R) {
+            sf_gload4(h_ba0, ba); sf_gload4(h_ba1, ba + 1);
+            sf_gload4(h_w00, wb); sf_gload4(h_w01, wb + 1); sf_gload4(h_w10, wb + 2); sf_gload4(h_w11, wb + 3);
+            sf_gload4(h_bb0, bb); sf_gload4(h_bb1, bb + 1);
         }
+        ring_start();
+        sf_wait<RING>();
 #pragma unroll
-        for (int r = 0; r < R; ++r) *reinterpret_cast<f32x4*>(&part[kq][r][4 * c4]) = acc[r];
-    };
-    // weight matrix of pass p: forward layers 2..L use Wh[0..L-2]; backward L..2 use WhT[L-2..0]
-    const int n_pass = TRAIN ? 2 * (L - 1) : (L - 1);
-    auto wseq = [&](int p) -> const float* {
-        if (p >= n_pass) return Wh;                      // dummy prefetch after the last pass
-        return p < L - 1 ? Wh + (int64_t)p * HH : WhT + (int64_t)(2 * (L - 1) - 1 - p) * HH;
-    };
-    load_chunk(wseq(0), 0, bufA);
-    load_chunk(wseq(0), 1, bufB);
-    auto reduced = [&](int r, int n) {     // fixed-order sum over the k-groups
-        float s = 0.f;
+        for (int o = 0; o < NO; ++o) sf_landed(a1v[o]);
+        sf_landed(yrow);
+        sf_landed(h_wa0); sf_landed(h_wa1);
+        sf_landed(h_ba0); sf_landed(h_ba1); sf_landed(h_w00); sf_landed(h_w01); sf_landed(h_w10); sf_landed(h_w11);
+        sf_landed(h_bb0); sf_landed(h_bb1);
+        // the labels of this block's rows: younger than the ring's first requests, landed with the first pass's operands
+        if (has_y) { sf_gload4(h_y0, Y + (int64_t)(int32_t)yrow * 2); sf_gload4(h_y1, Y + (int64_t)(int32_t)yrow * 2 + 1); }
 #pragma unroll
-        for (int g = 0; g < KG; ++g) s += part[g][r][n];
-        return s;
-    };
-
-    // per-thread output slots of the epilogues: element i = t + SF_THREADS*o of the R x Hp block
-    constexpr int NO = (R * Hp + SF_THREADS - 1) / SF_THREADS;
-    // head operands requested now; consumed after the forward chain
-    float h_wa0 = 0.f, h_wa1 = 0.f;
-    if (t < Hp) { h_wa0 = wa[2 * t]; h_wa1 = wa[2 * t + 1]; }
-    float h_ba0 = 0.f, h_ba1 = 0.f, h_w00 = 0.f, h_w01 = 0.f, h_w10 = 0.f, h_w11 = 0.f, h_bb0 = 0.f, h_bb1 = 0.f;
-    float h_y0 = 0.f, h_y1 = 0.f;
-    if (t < R) {
-        h_ba0 = ba[0]; h_ba1 = ba[1]; h_w00 = wb[0]; h_w01 = wb[1]; h_w10 = wb[2]; h_w11 = wb[3];
-        h_bb0 = bb[0]; h_bb1 = bb[1];
-        if (Y != nullptr && r0 + t < n_b) { h_y0 = Y[(int64_t)rows[r0 + t] * 2]; h_y1 = Y[(int64_t)rows[r0 + t] * 2 + 1]; }
+        for (int o = 0; o < NO; ++o) {
+            const int i = t + SF_THREADS * o;
+            if (stage && i < R * Hp) act[i / Hp][i % Hp] = a1v[o];
+        }
     }
+    lds_barrier();      // act is LDS: nothing here waits for the ring
 
     // ---------------- forward: layers 2..L
     for (int l = 2; l <= L; ++l) {
         const float* bias = bh + (int64_t)(l - 2) * Hp;
         const bool dr = TRAIN && mask != nullptr && l == n_pre;
-        float e_bias[NO], e_keep[NO];
+        float e_bias[NO];
+        uint32_t e_m[NO];
+        contract(wseq(l - 2), wseq(l - 1), [&]() {
 #pragma unroll
-        for (int o = 0; o < NO; ++o) {          // epilogue operands requested before the contraction
-            const int i = t + SF_THREADS * o;
-            e_bias[o] = 0.f; e_keep[o] = 1.f;
-            if (i < R * Hp) {
-                e_bias[o] = bias[i % Hp];
-                if (dr) e_keep[o] = mask[(int64_t)(r0 + i / Hp) * Hp + i % Hp] ? keep_scale : 0.f;
+            for (int o = 0; o < NO; ++o) {
+                const int i = (t + SF_THREADS * o) % (R * Hp);
+                e_bias[o] = 0.f;
+                sf_gload4(e_bias[o], bias + i % Hp);
+                e_m[o] = 1;
+                if (dr) sf_gload1(e_m[o], mask + (int64_t)(r0 + i / Hp) * Hp + i % Hp);
             }
-        }
-        contract(wseq(l - 2), wseq(l - 1));
+        });
         lds_barrier();
+        sf_wait<RING>();        // the epilogue's operands: RING requests are younger
+#pragma unroll
+        for (int o = 0; o < NO; ++o) { sf_landed(e_bias[o]); sf_landed(e_m[o]); }
+        sf_landed(h_y0); sf_landed(h_y1);
         float* aout = acts + (int64_t)(l - 1) * blk;
 #pragma unroll
         for (int o = 0; o < NO; ++o) {
@@ -212,7 +377,7 @@ __global__ __launch_bounds__(SF_THREADS) void stack_fused_kernel(
                 if (TRAIN) aout[gi] = a;
                 float nx = a;
                 if (dr) {
-                    nx = a * e_keep[o];
+                    nx = a * (e_m[o] ? keep_scale : 0.f);
                     adrop[gi] = nx;
                 }
                 act[r][n] = nx;
@@ -248,7 +413,7 @@ __global__ __launch_bounds__(SF_THREADS) void stack_fused_kernel(
             const bool valid = b < n_b;
             if (valid && Y != nullptr) {
                 const float e0 = y20 - h_y0, e1 = y21 - h_y1;
-                d = sqrtf(fmaxf(e0 * e0 + e1 * e1, 0.f));
+                d = sqrtf(fmaxf(TRAIN ? sf_sumsq_train(e0, e1) : sf_sumsq_eval(e0, e1), 0.f));
                 if (d > 0.f) { g0 = e0 / d / (float)n_b; g1 = e1 / d / (float)n_b; }
             }
             if (TRAIN) {
@@ -263,16 +428,23 @@ __global__ __launch_bounds__(SF_THREADS) void stack_fused_kernel(
         }
         lds_barrier();
     }
-    if (!TRAIN) return;
+    if (!TRAIN) {
+        ring_end();
+        return;
+    }
 
     // ---------------- dz_L = (dy1 . Wa^T) * ELU'(a_L), then backward through layers L..2
     {
         float* dzo = dz + (int64_t)(L - 1) * blk;
-        for (int i = t; i < R * Hp; i += SF_THREADS) {
-            const int r = i / Hp, k = i % Hp;
-            const float v = (hs[r][0] * wa[2 * k] + hs[r][1] * wa[2 * k + 1]) * elu_grad_from_act(act[r][k]);   // wa: L1/L2 hit
-            dzo[(int64_t)(r0 + r) * Hp + k] = v;
-            part[0][r][k] = v;     // staged; copied into act after the barrier (act is still being read)
+#pragma unroll
+        for (int o = 0; o < NO; ++o) {
+            const int i = t + SF_THREADS * o;
+            if (i < R * Hp) {
+                const int r = i / Hp, k = i % Hp;           // wa[2k], wa[2k + 1]: in registers since the prologue
+                const float v = (hs[r][0] * h_wa0 + hs[r][1] * h_wa1) * elu_grad_from_act(act[r][k]);
+                dzo[(int64_t)(r0 + r) * Hp + k] = v;
+                part[0][r][k] = v;     // staged; copied into act after the barrier (act is still being read)
+            }
         }
         lds_barrier();
         for (int i = t; i < R * Hp; i += SF_THREADS) act[i / Hp][i % Hp] = part[0][i / Hp][i % Hp];
@@ -282,33 +454,40 @@ __global__ __launch_bounds__(SF_THREADS) void stack_fused_kernel(
         const int p = (L - 1) + (L - l);             // pass index of this backward layer
         const float* aprev = acts + (int64_t)(l - 2) * blk;      // ELU output of layer l-1 (pre-dropout)
         const bool dr = mask != nullptr && l - 1 == n_pre;
-        float e_g[NO];
+        float e_a[NO];
+        uint32_t e_m[NO];
+        // sum_n dz_l[r][n] * W_l[k][n] = dz_l . (W_l^T)[n][k]
+        contract(wseq(p), wseq(p + 1), [&]() {
 #pragma unroll
-        for (int o = 0; o < NO; ++o) {          // epilogue operands requested before the contraction
-            const int i = t + SF_THREADS * o;
-            e_g[o] = 0.f;
-            if (i < R * Hp) {
+            for (int o = 0; o < NO; ++o) {
+                const int i = (t + SF_THREADS * o) % (R * Hp);
                 const int64_t gi = (int64_t)(r0 + i / Hp) * Hp + i % Hp;
-                float keep = 1.f;
-                if (dr) keep = mask[gi] ? keep_scale : 0.f;
-                e_g[o] = keep * elu_grad_from_act(aprev[gi]);
+                e_a[o] = 0.f;
+                sf_gload4(e_a[o], aprev + gi);
+                e_m[o] = 1;
+                if (dr) sf_gload1(e_m[o], mask + gi);
             }
-        }
-        contract(wseq(p), wseq(p + 1));              // sum_n dz_l[r][n] * W_l[k][n] = dz_l . (W_l^T)[n][k]
+        });
         lds_barrier();
+        sf_wait<RING>();        // the epilogue's operands: RING requests are younger
+#pragma unroll
+        for (int o = 0; o < NO; ++o) { sf_landed(e_a[o]); sf_landed(e_m[o]); }
         float* dzo = dz + (int64_t)(l - 2) * blk;
 #pragma unroll
         for (int o = 0; o < NO; ++o) {
             const int i = t + SF_THREADS * o;
             if (i < R * Hp) {
                 const int r = i / Hp, k = i % Hp;
-                const float v = reduced(r, k) * e_g[o];
+                float keep = 1.f;
+                if (dr) keep = e_m[o] ? keep_scale : 0.f;
+                const float v = reduced(r, k) * (keep * elu_grad_from_act(e_a[o]));
                 dzo[(int64_t)(r0 + r) * Hp + k] = v;
                 act[r][k] = v;
             }
         }
         lds_barrier();
     }
+    ring_end();
 }
 
 // Everything that reduces over the batch rows, for all hidden layers at once: see stack_tail.h (stack_dw_all_body).
@@ -350,11 +529,13 @@ extern "C" int loc_transpose_hidden(const float* Wh, float* WhT, int Hp, int n_h
 
 constexpr int SF_R = 2;   // batch rows per workgroup -> 16 workgroups per 32-row block
 // rows per workgroup of the TRAINING launch (loc_tuning.stack_train_rows).  A worker is bound by its weight stream (4.7 MB of
-// Wh + WhT from its XCD's L2, ~43 us at 110 GB/s per compute unit) whatever its row count, and the rows' arithmetic that does
-// not overlap with the stream comes on top: measured at the metric's shape (bench.py, 32-row steps, 12 helpers) 4 rows per
-// workgroup 189.9 us per step, 2 rows (rounds 1-4) 171.3, 1 row 162.4 (32 workers + helpers over two XCDs) - same bits.
-// One row per workgroup is ahead at every shape tried (profiles/r05_stack_train_rows.log): widths 64 / 128 / 512 +4 %,
-// 5,830 SNPs +10 %, 20,000 +9 %, 500,000 +1 %, --batch_size 64 +1.7 %, 128 +0.8 %.
+// Wh + WhT from its XCD's L2) whatever its row count, and what a pass does between its last and the next pass's first slot -
+// the reduction, two barriers, the epilogue - comes on top, longer with every row: measured at the metric's shape (bench.py,
+// 32-row steps, 12 helpers, round 5) 4 rows per workgroup 189.9 us per step, 2 rows (rounds 1-4) 171.3, 1 row 162.4 (32 workers +
+// helpers over two XCDs) - same bits.  One row per workgroup is ahead at every shape tried (profiles/r05_stack_train_rows.log):
+// widths 64 / 128 / 512 +4 %, 5,830 SNPs +10 %, 20,000 +9 %, 500,000 +1 %, --batch_size 64 +1.7 %, 128 +0.8 %.  Round 7's register
+// ring took the one-row kernel from 42.8 to 40.3 us (step 163.6 -> 161.2); the stream alone (no FMA, reduction, barrier or
+// epilogue) is ~33 us, the L2 port's rate (profiles/r07_stack_stream_floor.txt).
 static int sf_train_rows(const loc_tuning* tune, int n_b) {
     const int v = tune ? tune->stack_train_rows : 0;
     (void)n_b;
@@ -362,7 +543,9 @@ static int sf_train_rows(const loc_tuning* tune, int n_b) {
 }
 
 // L2 warm-up helper workgroups and XCD placement stride of the fused stack: speed hints (loc_tuning), defaults
-// measured at width 256: helpers 0 -> 78.6 us, 4 -> 63, 8 -> 51.7, 12 -> 51.0, 32 -> 55
+// measured at width 256: helpers 0 -> 78.6 us, 4 -> 63, 8 -> 51.7, 12 -> 51.0, 32 -> 55 (round 3, two rows per workgroup);
+// re-swept on the ring kernel (round 7, profiles/r07_stack_helpers.txt): 8 helpers 0.7 % behind 12, 16 and 20 within the
+// repetitions' spread of 12, stride 4 = stride 8 - unchanged
 static int sf_helpers(const loc_tuning* tune) {
     if (!tune || tune->stack_helpers == 0) return 12;
     return tune->stack_helpers < 0 ? 0 : tune->stack_helpers;
@@ -378,8 +561,9 @@ extern "C" int loc_stack_forward_backward(const float* a1_in, const float* Wh, c
                                           int slot_rows, const int32_t* rows, const float* Y, float* acts,
                                           float* adrop, float* dz, float* head_out, const loc_tuning* tune,
                                           void* stream) {
-    if (n_b < 1 || n_b > slot_rows || slot_rows % 32) {
-        loc_set_error("loc_stack_forward_backward: n_b=%d, slot_rows=%d", n_b, slot_rows);
+    // L >= 2: the kernel has at least one layer pass (the labels and the ring are waited for inside the passes)
+    if (n_b < 1 || n_b > slot_rows || slot_rows % 32 || L < 2) {
+        loc_set_error("loc_stack_forward_backward: n_b=%d, slot_rows=%d, L=%d", n_b, slot_rows, L);
         return -1;
     }
     // every row of the row blocks in use is carried (rows >= n_b get a zero loss gradient), so the tail and the
@@ -418,6 +602,10 @@ static int sf_eval_launch(const float* a1, const float* rd_partial, int rd_G, in
     // covers the rows, above 8 x compute units rows 16 or 32 rows per workgroup on the fp32 matrix pipe, stack_rows.hip: the
     // measured round times are there); 1 = always the 32-row matrix-pipe form (where supported), 2 = always the 16-row form;
     // -1 = always 2 rows per workgroup on the vector ALU, -2 = 4 rows, -3 = 8 rows (measurement / tests)
+    if (L < 2) {        // the kernel has at least one layer pass (the labels and the ring are waited for inside the passes)
+        loc_set_error("hidden stack of a predict: L=%d (needs at least one hidden layer pass)", L);
+        return -1;
+    }
     if (rows_form >= 0 && loc_stack_rows_supported(Hp, L) && (rows_form > 0 || n_b >= loc_stack_rows_min_rows()))
         return sr_eval_launch(a1, rd_partial, rd_G, rd_MH, rd_cvec8, rd_b1, Wh, bh, wa, ba, wb, bb, L, n_b, rows, Y, yhat, dist,
                               rows_form == 1 ? 32 : rows_form == 2 ? 16 : 0, stream);
