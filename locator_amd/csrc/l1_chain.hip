@@ -49,8 +49,6 @@
 #include "common.h"
 #include "stack_tail.h"
 
-#define KT 32
-
 // timing ablations (make ablate_chain A=<bits>): results are WRONG with any bit set; they only answer "what does this
 // part of the loop cost".  1 = no barrier, 2 = no per-tile small operands, 4 = no next-forward part, 16 = no Adam
 // arithmetic, 32 = no weight stores
@@ -58,61 +56,9 @@
 #define LOC_CHAIN_ABLATE 0
 #endif
 
-__device__ __forceinline__ void ch_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ void ch_adam_fast(float& w, float& m, float& v, float g, float alpha) {
-    m = m + (g - m) * ADAM_C1;
-    v = v + (g * g - v) * ADAM_C2;
-    w = w - (m * alpha) * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(v) + ADAM_EPS);
-}
-
-// Vector-memory loads the compiler does not track, with hand-counted s_waitcnt (as in l1_gemm.hip).  Left to itself the
-// compiler waits for the 12 KB prefetch it has just issued before the first use of the CURRENT register set (its
-// per-register wait counts are merged conservatively around the loop), so nothing overlaps.  The "memory" clobbers keep
-// these loads, the compiler's own stores and the waits in program order, which is what the counts below rely on.
-// Every untracked load is issued UNCONDITIONALLY (a dummy address where there is nothing to fetch): the compiler believes
-// an asm output is valid at once, so a load under a branch would meet "not loaded" in a phi, and a copy inserted for that
-// phi would read the register before the data lands.  tests/test_chain_asm.py checks the generated code for exactly that.
-// 16 bytes at (wave-uniform base) + (32-bit byte offset of the lane) + OFF: one offset register serves W1, m and v
-template <int OFF, bool NT>
-__device__ __forceinline__ void ch_gload16(f32x4& v, const float* base, uint32_t voff) {
-    if (NT) asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3 nt" : "=v"(v) : "v"(voff), "s"(base), "n"(OFF) : "memory");
-    else asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(v) : "v"(voff), "s"(base), "n"(OFF) : "memory");
-}
-// The two wait states behind the store are part of it: on gfx940+ a vector-memory store of more than 8 bytes still reads its
-// data registers for two wait states after it issues, and a vector-ALU write to them in that window corrupts what is
-// stored.  The compiler's hazard recognizer pads its OWN stores; it cannot see into an asm statement, and once the data
-// registers are dead after the asm it is free to reuse them at once - round 4's register allocation of the second step did
-// (`v_pk_add_f32 v[24:25]` right behind `global_store_dwordx4 v142, v[22:25]`: wrong Adam moments in memory, right weights).
-template <int OFF, bool NT>
-__device__ __forceinline__ void ch_gstore16(const f32x4& v, float* base, uint32_t voff) {
-    if (NT) asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 nt\n\ts_nop 1" : : "v"(voff), "v"(v), "s"(base), "n"(OFF) : "memory");
-    else asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3\n\ts_nop 1" : : "v"(voff), "v"(v), "s"(base), "n"(OFF) : "memory");
-}
-// 4 bytes at a per-lane 64-bit address
-__device__ __forceinline__ void ch_gload4(uint32_t& v, const void* p) {
-    asm volatile("global_load_dword %0, %1, off" : "=v"(v) : "v"(p) : "memory");
-}
-// Wait until at most N vector-memory operations are outstanding; the operands tie the registers the wait protects, so
-// no use of them can be scheduled above it.  COUNTING RULE (gfx9 has one counter for loads and stores): loads retire in
-// order among loads and stores among stores, but a store may retire before an older load.  So "at most N outstanding"
-// proves that a load has landed only if N is the number of LOADS issued after it -- stores never count.
-// (a -DLOC_CHAIN_DEBUG_DRAIN build - `make debug_drain`, the parity-debug twin library - turns every hand count into
-// vmcnt(0); tests/test_gpu_chain.py compares the two builds bit for bit)
-#ifdef LOC_CHAIN_DEBUG_DRAIN
-#define CH_VMCNT(N) 0
-#else
-#define CH_VMCNT(N) (N)
-#endif
-template <int N>
-__device__ __forceinline__ void ch_wait_unit(f32x4 (&a)[4], f32x4 (&b)[4], f32x4 (&c)[4], uint32_t& s0, uint32_t& s1,
-                                             uint32_t& s2) {
-    asm volatile("s_waitcnt vmcnt(%15)"
-                 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]),
-                   "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(s0), "+v"(s1), "+v"(s2)
-                 : "n"(CH_VMCNT(N))
-                 : "memory");
-}
+// The weight / moment stream and the small operands are untracked loads with ONE hand-counted wait per unit
+// (gload16_uniform, gload4_fresh, gstore16_uniform, vm_wait_unit: common.h, with the counting rule).  Every one of them is
+// issued UNCONDITIONALLY, on a dummy address where there is nothing to fetch.
 
 constexpr int CH_TP = 33;
 constexpr int CH_SM = 896;   // floats of one k-tile's small operands in LDS (see `sm` in the kernel)
@@ -124,33 +70,6 @@ constexpr int ch_smf(int rb) { return CH_SM + 512 * (rb - 1); }       // floats 
 constexpr size_t ch_lds_floats(int nht, int rb = 1) {
     return 32 * rb * (nht * 32 + 1) + 64 * rb + 8 * ch_upw(nht) * 32 * CH_TP + 2 * 8 * 64 + 8 * 64 + 2 * ch_ktw(nht) * ch_smf(rb) +
            ((nht != 8 || rb > 1) ? nht * 32 : 0);
-}
-
-// The hand-counted wait: at most N vector-memory operations outstanding; the operands tie every register an untracked load
-// of this wave may still be writing (the current unit's three register sets and the small-operand words of its loader
-// roles), so no use of them can be scheduled above it.
-template <int N>
-__device__ __forceinline__ void ch_wait_unit(f32x4 (&a)[4], f32x4 (&b)[4], f32x4 (&c)[4], uint32_t (&ld)[1][3]) {
-    ch_wait_unit<N>(a, b, c, ld[0][0], ld[0][1], ld[0][2]);
-}
-template <int N>
-__device__ __forceinline__ void ch_wait_unit(f32x4 (&a)[4], f32x4 (&b)[4], f32x4 (&c)[4], uint32_t (&ld)[2][3]) {
-    asm volatile("s_waitcnt vmcnt(%18)"
-                 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]),
-                   "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(ld[0][0]), "+v"(ld[0][1]), "+v"(ld[0][2]),
-                   "+v"(ld[1][0]), "+v"(ld[1][1]), "+v"(ld[1][2])
-                 : "n"(CH_VMCNT(N))
-                 : "memory");
-}
-template <int N>
-__device__ __forceinline__ void ch_wait_unit(f32x4 (&a)[4], f32x4 (&b)[4], f32x4 (&c)[4], uint32_t (&ld)[4][3]) {
-    asm volatile("s_waitcnt vmcnt(%24)"
-                 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]),
-                   "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(ld[0][0]), "+v"(ld[0][1]), "+v"(ld[0][2]),
-                   "+v"(ld[1][0]), "+v"(ld[1][1]), "+v"(ld[1][2]), "+v"(ld[2][0]), "+v"(ld[2][1]), "+v"(ld[2][2]),
-                   "+v"(ld[3][0]), "+v"(ld[3][1]), "+v"(ld[3][2])
-                 : "n"(CH_VMCNT(N))
-                 : "memory");
 }
 
 template <int NTM, int NHT, int RB>
@@ -218,10 +137,10 @@ __global__ __launch_bounds__(512) void l1_bwd_adam_chain_kernel(
         // ONE address for the whole wave (one 16-byte request each instead of 1 KB), a different line per wave so that
         // the 2048 waves do not queue on one channel; results unused
         const uint32_t o = kt >= 0 ? unit_off(kt, ut) : (uint32_t)((((uint32_t)blockIdx.x * 8 + w) & 2047u) * 64u);
-        ch_gload16<0, (NTM & 2) != 0>(wq[0], w1s, o);    ch_gload16<0, (NTM & 1) != 0>(mq[0], m1s, o);    ch_gload16<0, (NTM & 1) != 0>(vq[0], v1s, o);
-        ch_gload16<1024, (NTM & 2) != 0>(wq[1], w1s, o); ch_gload16<1024, (NTM & 1) != 0>(mq[1], m1s, o); ch_gload16<1024, (NTM & 1) != 0>(vq[1], v1s, o);
-        ch_gload16<2048, (NTM & 2) != 0>(wq[2], w1s, o); ch_gload16<2048, (NTM & 1) != 0>(mq[2], m1s, o); ch_gload16<2048, (NTM & 1) != 0>(vq[2], v1s, o);
-        ch_gload16<3072, (NTM & 2) != 0>(wq[3], w1s, o); ch_gload16<3072, (NTM & 1) != 0>(mq[3], m1s, o); ch_gload16<3072, (NTM & 1) != 0>(vq[3], v1s, o);
+        gload16_uniform<0, (NTM & 2) != 0>(wq[0], w1s, o);    gload16_uniform<0, (NTM & 1) != 0>(mq[0], m1s, o);    gload16_uniform<0, (NTM & 1) != 0>(vq[0], v1s, o);
+        gload16_uniform<1024, (NTM & 2) != 0>(wq[1], w1s, o); gload16_uniform<1024, (NTM & 1) != 0>(mq[1], m1s, o); gload16_uniform<1024, (NTM & 1) != 0>(vq[1], v1s, o);
+        gload16_uniform<2048, (NTM & 2) != 0>(wq[2], w1s, o); gload16_uniform<2048, (NTM & 1) != 0>(mq[2], m1s, o); gload16_uniform<2048, (NTM & 1) != 0>(vq[2], v1s, o);
+        gload16_uniform<3072, (NTM & 2) != 0>(wq[3], w1s, o); gload16_uniform<3072, (NTM & 1) != 0>(mq[3], m1s, o); gload16_uniform<3072, (NTM & 1) != 0>(vq[3], v1s, o);
     };
     // The first unit is requested before anything else; the prologue ends with vmcnt(0).
     f32x4 wA[4], mA[4], vA[4], wB[4], mB[4], vB[4];
@@ -294,7 +213,7 @@ __global__ __launch_bounds__(512) void l1_bwd_adam_chain_kernel(
                     a0 = next_stats + (int64_t)hi * Kp + k; a1 = a0; a2 = a0;
                 }
             }
-            ch_gload4(ld[rr][0], a0); ch_gload4(ld[rr][1], a1); ch_gload4(ld[rr][2], a2);
+            gload4_fresh(ld[rr][0], a0); gload4_fresh(ld[rr][1], a1); gload4_fresh(ld[rr][2], a2);
         }
     };
     auto stage = [&](int buf, int T) {
@@ -331,10 +250,10 @@ __global__ __launch_bounds__(512) void l1_bwd_adam_chain_kernel(
     {
         const int T0 = blockIdx.x;
         fetch(T0);
-        ch_wait_unit<0>(wA, mA, vA, ld);
+        vm_wait_unit<0>(wA, mA, vA, ld);
         stage(0, T0);
         fetch(T0 + G);                                          // staged during the first iteration
-        ch_wait_unit<0>(wA, mA, vA, ld);
+        vm_wait_unit<0>(wA, mA, vA, ld);
     }
     __syncthreads();
 
@@ -412,7 +331,7 @@ __global__ __launch_bounds__(512) void l1_bwd_adam_chain_kernel(
         // outstanding" proves every older load landed -- this unit (requested an iteration ago) and the next tile's small
         // operands ld0..2 (requested at the end of the previous iteration).
         load_unit(ktile(T_pref, kq), ut0 + WPS * ((SUB + 1) % UPW), wn, mn, vn);
-        ch_wait_unit<12>(wq, mq, vq, ld);
+        vm_wait_unit<12>(wq, mq, vq, ld);
 
         // ONE fp32 MFMA chain per unit:  Gn[h][k] = sum_b dZ[b][h] xn[b][k]  (D[i = unit][j = SNP], contraction over the
         // batch rows b = rowmap(s, hi); xn = (x - mean) * rstd).  Everything else follows from it without forming dxhat
@@ -450,7 +369,7 @@ __global__ __launch_bounds__(512) void l1_bwd_adam_chain_kernel(
 #if LOC_CHAIN_ABLATE & 16
                 wv += g[q * 4 + c];
 #else
-                ch_adam_fast(wv, mv, vv, g[q * 4 + c], alpha);
+                adam_update_fast(wv, mv, vv, g[q * 4 + c], alpha);
 #endif
                 wq[q][c] = wv; mq[q][c] = mv; vq[q][c] = vv;
             }
@@ -461,10 +380,10 @@ __global__ __launch_bounds__(512) void l1_bwd_adam_chain_kernel(
 #else
         // (stores never enter the load count - see the counting rule - so a missing slot may simply skip them)
         if (!valid) { adam4(0); adam4(1); adam4(2); adam4(3); } else {
-        adam4(0); ch_gstore16<0, (NTM & 4) != 0>(wq[0], w1s, so);    ch_gstore16<0, (NTM & 8) != 0>(mq[0], m1s, so);    ch_gstore16<0, (NTM & 8) != 0>(vq[0], v1s, so);
-        adam4(1); ch_gstore16<1024, (NTM & 4) != 0>(wq[1], w1s, so); ch_gstore16<1024, (NTM & 8) != 0>(mq[1], m1s, so); ch_gstore16<1024, (NTM & 8) != 0>(vq[1], v1s, so);
-        adam4(2); ch_gstore16<2048, (NTM & 4) != 0>(wq[2], w1s, so); ch_gstore16<2048, (NTM & 8) != 0>(mq[2], m1s, so); ch_gstore16<2048, (NTM & 8) != 0>(vq[2], v1s, so);
-        adam4(3); ch_gstore16<3072, (NTM & 4) != 0>(wq[3], w1s, so); ch_gstore16<3072, (NTM & 8) != 0>(mq[3], m1s, so); ch_gstore16<3072, (NTM & 8) != 0>(vq[3], v1s, so);
+        adam4(0); gstore16_uniform<0, (NTM & 4) != 0>(wq[0], w1s, so);    gstore16_uniform<0, (NTM & 8) != 0>(mq[0], m1s, so);    gstore16_uniform<0, (NTM & 8) != 0>(vq[0], v1s, so);
+        adam4(1); gstore16_uniform<1024, (NTM & 4) != 0>(wq[1], w1s, so); gstore16_uniform<1024, (NTM & 8) != 0>(mq[1], m1s, so); gstore16_uniform<1024, (NTM & 8) != 0>(vq[1], v1s, so);
+        adam4(2); gstore16_uniform<2048, (NTM & 4) != 0>(wq[2], w1s, so); gstore16_uniform<2048, (NTM & 8) != 0>(mq[2], m1s, so); gstore16_uniform<2048, (NTM & 8) != 0>(vq[2], v1s, so);
+        adam4(3); gstore16_uniform<3072, (NTM & 4) != 0>(wq[3], w1s, so); gstore16_uniform<3072, (NTM & 8) != 0>(mq[3], m1s, so); gstore16_uniform<3072, (NTM & 8) != 0>(vq[3], v1s, so);
         }
 #endif
         if (chain && valid && !(LOC_CHAIN_ABLATE & 4)) {
@@ -479,7 +398,7 @@ __global__ __launch_bounds__(512) void l1_bwd_adam_chain_kernel(
 #if !(LOC_CHAIN_ABLATE & 1)
         // every wave's (dgamma | dbeta) partial of this k-tile and the next tile's small operands are in LDS; all reads
         // of this tile's small operands are above this line, so the buffer is free for tile + 2 after it
-        ch_lds_barrier();
+        lds_barrier();
 #endif
 
         float dsum = red[(par * 8 + kq * WPS) * 64 + lane];       // the waves of this slot, in wave order

@@ -65,9 +65,6 @@
 #define GM_AIMG (GM_BM * GM_BK * 2)  /* 16384: bf16 genotype image of one SNP block    */
 #define GM_LDS 131072                /* 4 genotype images in the loop; the epilogue stages 8 x 16 KB of partials */
 
-__device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ uint32_t rne16g(uint32_t u) { return u + 0x7FFFu + ((u >> 16) & 1u); }
-
 // ---------------------------------------------------------------------------------------------------------
 // weight image
 // ---------------------------------------------------------------------------------------------------------
@@ -98,7 +95,7 @@ __global__ __launch_bounds__(GM_HP) void l1_image_kernel(const float* __restrict
 #pragma unroll
                 for (int p = 0; p < P; ++p) {
                     uint32_t u = fbits(r);
-                    if (p == P - 1 && P < 3) u = rne16g(u);
+                    if (p == P - 1 && P < 3) u = rne16(u);
                     pc[p][e] = u >> 16;
                     if (p < P - 1) r -= bitsf(u & 0xFFFF0000u);
                 }
@@ -150,9 +147,6 @@ __global__ __launch_bounds__(1024) void l1_image_cvec_kernel(const float* __rest
 // ---------------------------------------------------------------------------------------------------------
 // GEMM
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t lds_addr32(const void* p) {
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
-}
 // four A fragments (row tiles 0..3 of one k-step) by four 16-byte LDS reads; volatile so that they stay in the load
 // phase, ahead of the barrier that hands the matrix pipe to this wave
 __device__ __forceinline__ void rd4(bf16x8& a0, bf16x8& a1, bf16x8& a2, bf16x8& a3, uint32_t addr) {
@@ -160,9 +154,11 @@ __device__ __forceinline__ void rd4(bf16x8& a0, bf16x8& a1, bf16x8& a2, bf16x8& 
                  "ds_read_b128 %2, %4 offset:1024\n\tds_read_b128 %3, %4 offset:1536"
                  : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3) : "v"(addr) : "memory");
 }
-// Global loads as asm with hand-counted s_waitcnt vmcnt: the compiler's own bookkeeping merges the prologue's and the
-// loop's in-flight state at the loop header and then waits for almost everything in the first blocks of every
-// unrolled body (seen as vmcnt(2) where 9 loads may stay in flight).  The counts are in the loop below.
+// Global loads as asm (gload16_lane) with hand-counted waits (vm_wait_fenced; the barrier is lds_barrier_fenced: LDS traffic
+// of this wave done, then the workgroup barrier, no vmcnt wait: weight / genotype requests stay in flight): the compiler's
+// own bookkeeping merges the prologue's and the loop's in-flight state at the loop header and then waits for almost
+// everything in the first blocks of every unrolled body (seen as vmcnt(2) where 9 loads may stay in flight).  The
+// primitives and the counting rule are in common.h, the counts in the loop below.
 // COUNT TABLE (per wave, requests in program order; P = pieces, 4 fragments per (block, piece) tile):
 //   load phase of a block      1 genotype request (load_x)
 //   matrix phase of a block    P tiles x 4 fragment requests (load_b_part), each issued right after the 4 MFMAs that
@@ -172,29 +168,8 @@ __device__ __forceinline__ void rd4(bf16x8& a0, bf16x8& a1, bf16x8& a2, bf16x8& 
 //   wait before a fragment     requested three tiles ago: 11 younger fragment requests plus one genotype request per
 //                              block boundary crossed on the way (P = 1: three, P = 2: two for piece 0 and one for
 //                              piece 1, P = 3: one)                                           -> vmcnt(14 | 13 | 12)
-// Editing the request order in block() means re-deriving these; a -DLOC_GEMM_DEBUG_DRAIN build turns every count into
-// vmcnt(0) for parity debugging.
-template <typename T>
-__device__ __forceinline__ void gload16(T& r, const void* p) {
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(r) : "v"(p) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-#ifdef LOC_GEMM_DEBUG_DRAIN
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-#endif
-    __builtin_amdgcn_sched_barrier(0);
-}
-// LDS traffic of this wave done, then the workgroup barrier (no vmcnt wait: weight / genotype requests stay in flight)
-// and nothing (MFMAs included) scheduled across it
-__device__ __forceinline__ void phase_barrier() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-
+// Editing the request order in block() means re-deriving these; a -DLOC_DEBUG_DRAIN build (make debug_drain) turns every
+// count into vmcnt(0) for parity debugging.
 template <int P>
 __global__ __launch_bounds__(GM_NT) void l1_gemm_kernel(const uint8_t* __restrict__ X, int64_t pitch,
                                                          const int32_t* __restrict__ rows, int n, int Kp,
@@ -233,7 +208,7 @@ __global__ __launch_bounds__(GM_NT) void l1_gemm_kernel(const uint8_t* __restric
         const int cc = c < cntp ? c : cntp - 1;
         int koff = (g + cc * G) * (2 * GM_BK) + 16 * q;
         if (koff > Kp - 16) koff = Kp - 16;                    // only in the zero-weight padding of the last pair
-        gload16(R, xsrc[i] + koff);
+        gload16_lane(R, xsrc[i] + koff);
     };
     // image of block a: chunk c8 (8 SNPs) of row m at  c8*2048 + ((m ^ (c8 & 6) ^ (a & 1)) << 4)  - the 8 lanes of
     // one 16-byte store group (one row, both blocks of the pair) fall on 8 different 16-byte bank groups, and so do
@@ -262,7 +237,7 @@ __global__ __launch_bounds__(GM_NT) void l1_gemm_kernel(const uint8_t* __restric
         const int kt = 2 * (g + (a >> 1) * G) + (a & 1);
         const unsigned char* src = tiles + ((int64_t)kt * P + p) * GM_BTILE + b_lane;
 #pragma unroll
-        for (int kk = k0; kk < k1; ++kk) gload16(R.b[kk], src + kk * 8192);
+        for (int kk = k0; kk < k1; ++kk) gload16_lane(R.b[kk], src + kk * 8192);
     };
 
     f32x16 acc[4];
@@ -287,7 +262,7 @@ __global__ __launch_bounds__(GM_NT) void l1_gemm_kernel(const uint8_t* __restric
         load_b_part(B0, 0, 0, 4);
         load_b_part(B1, 1, 0, 4);
         load_b_part(B2, 2, 0, 4);
-        wait_vm<0>();
+        vm_wait_fenced<0>();
         widen(x0, 0, 0);
         widen(x1, 0, 1);
     }
@@ -300,7 +275,7 @@ __global__ __launch_bounds__(GM_NT) void l1_gemm_kernel(const uint8_t* __restric
     // tiles ahead.  The phases of the two groups alternate between the same barriers, so a SIMD's matrix pipe is
     // fed by one wave while its partner moves data.
     const int grp = w >> 2;
-    if (grp == 1) phase_barrier();
+    if (grp == 1) lds_barrier_fenced();
     constexpr int NBLK = (P == 3) ? 2 : 6;                      // unrolled blocks: register set and block parity static
     auto block = [&](int bb, auto alc) {
         constexpr int al = decltype(alc)::value;
@@ -311,10 +286,10 @@ __global__ __launch_bounds__(GM_NT) void l1_gemm_kernel(const uint8_t* __restric
         for (int kk = 0; kk < 4; ++kk) rd4(a[kk][0], a[kk][1], a[kk][2], a[kk][3], aoff[al & 1][kk] + so);
         // vmcnt is in order.  A block issues 1 genotype request, then 4 weight requests per tile.  The genotypes
         // widened now were requested two blocks ago: 4P + 1 + 4P younger requests may stay in flight.
-        wait_vm<8 * P + 1>();
+        vm_wait_fenced<8 * P + 1>();
         widen(XR[al & 1], (ai >> 1) + 1, al & 1);
         load_x(XR[al & 1], (ai >> 1) + 2, al & 1);
-        phase_barrier();
+        lds_barrier_fenced();
 #pragma unroll
         for (int p = 0; p < P; ++p) {
             const int u = al * P + p;
@@ -323,9 +298,9 @@ __global__ __launch_bounds__(GM_NT) void l1_gemm_kernel(const uint8_t* __restric
             for (int kk = 0; kk < 4; ++kk) {
                 // fragment kk of this tile was requested three tiles ago: 11 weight requests since, plus one genotype
                 // request per block boundary crossed on the way (p folds after unrolling)
-                if (P == 1) wait_vm<14>();
-                else if (P == 2 && p == 0) wait_vm<13>();
-                else wait_vm<12>();
+                if (P == 1) vm_wait_fenced<14>();
+                else if (P == 2 && p == 0) vm_wait_fenced<13>();
+                else vm_wait_fenced<12>();
 #pragma unroll
                 for (int tm = 0; tm < 4; ++tm)
                     acc[tm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[kk][tm], Bc.b[kk], acc[tm], 0, 0, 0);
@@ -334,7 +309,7 @@ __global__ __launch_bounds__(GM_NT) void l1_gemm_kernel(const uint8_t* __restric
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        phase_barrier();
+        lds_barrier_fenced();
     };
     // whole bodies without a branch inside (the compiler's vmcnt bookkeeping stays exact), then the remainder
     int bb = 0;
@@ -358,10 +333,10 @@ __global__ __launch_bounds__(GM_NT) void l1_gemm_kernel(const uint8_t* __restric
     }
     // requests past the end (clamped, never used) are still landing: drain them while their registers are still
     // allocated - the empty asm after the wait is what keeps the compiler from re-using one of them before it
-    wait_vm<0>();
+    vm_wait_fenced<0>();
     asm volatile("" ::"v"(B0.b[0]), "v"(B0.b[1]), "v"(B0.b[2]), "v"(B0.b[3]), "v"(B1.b[0]), "v"(B1.b[1]), "v"(B1.b[2]),
                  "v"(B1.b[3]), "v"(B2.b[0]), "v"(B2.b[1]), "v"(B2.b[2]), "v"(B2.b[3]), "v"(XR[0]), "v"(XR[1]));
-    if (grp == 0) phase_barrier();
+    if (grp == 0) lds_barrier_fenced();
 
     // D[i = row][j = unit]: wave tile 128 rows x 32 units through a wave-private LDS image, then 16-byte stores
     float* const ep = reinterpret_cast<float*>(gm_smem) + w * 4096;
@@ -466,20 +441,6 @@ int gm_launch_reduce(const float* partial, int G, int64_t MH, const float* cvec8
     return 0;
 }
 
-// the dynamic-LDS limit is a per-device attribute of the function: set once per (kernel, device)
-template <typename F>
-static int gm_set_lds(F* func) {
-    static bool done[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev >= 0 && dev < 64 && done[dev]) return 0;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(func), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       GM_LDS);
-    if (e != hipSuccess) { loc_set_error("hipFuncSetAttribute(%d): %s", GM_LDS, hipGetErrorString(e)); return (int)e; }
-    if (dev >= 0 && dev < 64) done[dev] = true;
-    return 0;
-}
-
 extern "C" int loc_l1_forward_gemm(const uint8_t* X, int64_t x_pitch, const int32_t* rows, int n, const loc_dims* d,
                                    const void* image, int pieces, const float* b1, float* partial,
                                    int64_t partial_floats, float* a1, int target_blocks, void* stream) {
@@ -507,8 +468,7 @@ extern "C" int loc_l1_forward_gemm(const uint8_t* X, int64_t x_pitch, const int3
     hipStream_t st = (hipStream_t)stream;
 #define GM_LAUNCH(PP)                                                                                          \
     {                                                                                                          \
-        int rc = gm_set_lds(l1_gemm_kernel<PP>);                                                               \
-        if (rc) return rc;                                                                                     \
+        LOC_ENSURE_LDS((l1_gemm_kernel<PP>), GM_LDS);                                                          \
         hipLaunchKernelGGL(l1_gemm_kernel<PP>, dim3(n_mt * G), dim3(GM_NT), GM_LDS, st, X, x_pitch, rows, n,   \
                            d->Kp, tiles, partial, G, n_mt, nkt / 2);                                           \
     }

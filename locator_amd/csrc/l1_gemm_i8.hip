@@ -331,9 +331,6 @@ __global__ __launch_bounds__(G8_HP) void l1_image_i8_kernel(const float* __restr
 // ---------------------------------------------------------------------------------------------------------
 // GEMM
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t lds_addr32_i8(const void* p) {
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
-}
 // the four A fragments (row tiles 0..3) of one 32-SNP step by four 16-byte LDS reads; volatile so that they stay in
 // the load phase, ahead of the barrier that hands the matrix pipe to this wave
 __device__ __forceinline__ void rd4_i8(i32x4& a0, i32x4& a1, i32x4& a2, i32x4& a3, uint32_t addr) {
@@ -341,8 +338,9 @@ __device__ __forceinline__ void rd4_i8(i32x4& a0, i32x4& a1, i32x4& a2, i32x4& a
                  "ds_read_b128 %2, %4 offset:8192\n\tds_read_b128 %3, %4 offset:12288"
                  : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3) : "v"(addr) : "memory");
 }
-// Global loads as asm with hand-counted s_waitcnt vmcnt (see l1_gemm.hip: the compiler's own counts collapse at the
-// loop header).  COUNT TABLE, per wave, requests in program order.  One iteration = one PAIR of 64-SNP blocks =
+// Global loads as asm with hand-counted waits (vm_wait_fenced, wait_lgkm0_fenced, lds_barrier_fenced: common.h, with the
+// counting rule; see l1_gemm.hip: the compiler's own counts collapse at the loop header).
+// COUNT TABLE, per wave, requests in program order.  One iteration = one PAIR of 64-SNP blocks =
 // 4 steps of 32 SNPs; a wave owns UT unit tiles (of 32 units); FP = 4 D UT digit fragments per pair, consumed in the
 // order (step, plane, unit tile); NB fragments in flight; DPW = 2 UT genotype DMAs per wave and pair:
 //   head of an iteration   DPW genotype DMAs (this wave's 16 UT rows of the pair G8_LA iterations ahead)
@@ -352,27 +350,7 @@ __device__ __forceinline__ void rd4_i8(i32x4& a0, i32x4& a1, i32x4& a2, i32x4& a
 //   => before the rendezvous of an iteration (after steps 0 and 1) the wave's DMAs of the NEXT pair must have landed:
 //      they were issued LA - 1 heads ago; younger are (LA - 1) later heads' DMAs, (LA - 1) whole iterations of FP
 //      fragment requests and the FP / 2 of steps 0, 1:                 vmcnt((LA - 1)(DPW + FP) + FP / 2)
-//   (a LOC_GEMM_DEBUG_DRAIN build replaces every count by vmcnt(0) for parity debugging: make debug_drain)
-template <int N>
-__device__ __forceinline__ void wait_vm_i8() {
-#ifdef LOC_GEMM_DEBUG_DRAIN
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-#endif
-    __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void wait_lgkm0_i8() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void barrier_i8() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
+//   (a LOC_DEBUG_DRAIN build replaces every count by vmcnt(0) for parity debugging: make debug_drain)
 // iteration heads between the request of fragment j of a pair and its consumption NB fragments later: a fragment
 // F = c FP + j is requested right after F - NB is consumed and the head of iteration c' sits just before fragment
 // c' FP, so the heads counted are those with F - NB < c' FP <= F:  ceil((NB - j) / FP)
@@ -450,7 +428,7 @@ __device__ __forceinline__ void g8_sweep(const g8_ctx& c, int plane0, i32x16 (&a
     // pairs per unrolled body, so that the ring slot of every fragment is static: the smallest UP with UP FP % NB == 0
     constexpr int UP = (FP % NB == 0) ? 1 : ((2 * FP) % NB == 0) ? 2 : ((3 * FP) % NB == 0) ? 3 : 4;
     static_assert((UP * FP) % NB == 0 && G8_RP >= G8_LA + 2 && G8_RPK >= G8_LA + 2, "ring / unroll shapes");
-    const uint32_t lds0 = lds_addr32_i8(c.As);
+    const uint32_t lds0 = lds_addr32(c.As);
     auto dma_x = [&](int pc, int i) {
         int cc = pc < c.cntp ? pc : c.cntp - 1;
         if (LOC_GEMM_ABLATE & 16) cc = 0;
@@ -518,12 +496,12 @@ __device__ __forceinline__ void g8_sweep(const g8_ctx& c, int plane0, i32x16 (&a
         for (int i = 0; i < DPW; ++i) dma_x(pc, i);
 #pragma unroll
     for (int f = 0; f < NB; ++f) load_b(B[f], pair_base(f / FP), voff[f % FP]);
-    wait_vm_i8<0>();
-    barrier_i8();
+    vm_wait_fenced<0>();
+    lds_barrier_fenced();
     if (PK) {                                               // pairs 0 and 1 expanded before the loop, pair pc + 2 inside it
         unpack(0);
         unpack(1);
-        barrier_i8();
+        lds_barrier_fenced();
     }
     rd4_i8(A[0][0], A[0][1], A[0][2], A[0][3], aoff[0]);
 
@@ -542,11 +520,11 @@ __device__ __forceinline__ void g8_sweep(const g8_ctx& c, int plane0, i32x16 (&a
 #pragma unroll
         for (int st = 0; st < 4; ++st) {
             if (st == 2 && !(LOC_GEMM_ABLATE & 4)) {
-                wait_vm_i8<N_DMA>();                        // my rows of pair pc + 1 (PK: packed pair pc + 2) are in the ring
-                barrier_i8();                               // ... and so are everyone's; nobody still reads pair pc - 1
+                vm_wait_fenced<N_DMA>();                        // my rows of pair pc + 1 (PK: packed pair pc + 2) are in the ring
+                lds_barrier_fenced();                               // ... and so are everyone's; nobody still reads pair pc - 1
                 //                                            (PK: and pair pc + 1, expanded during the last half pair, is complete)
             } else {
-                wait_lgkm0_i8();                            // A[st & 1] has landed
+                wait_lgkm0_fenced();                            // A[st & 1] has landed
             }
             if (LOC_GEMM_ABLATE & 8) {}
             else if (st < 3) rd4_i8(A[(st + 1) & 1][0], A[(st + 1) & 1][1], A[(st + 1) & 1][2], A[(st + 1) & 1][3], aoff[st + 1] + so);
@@ -560,12 +538,12 @@ __device__ __forceinline__ void g8_sweep(const g8_ctx& c, int plane0, i32x16 (&a
                     // static after unrolling: the if-chain stands in for a template argument that depends on loop variables
                     {
                         const int h = g8_heads(j, FP, NB);
-                        if (h == 0) wait_vm_i8<NB - 1>();
-                        else if (h == 1) wait_vm_i8<NB - 1 + DPW>();
-                        else if (h == 2) wait_vm_i8<NB - 1 + 2 * DPW>();
-                        else if (h == 3) wait_vm_i8<NB - 1 + 3 * DPW>();
-                        else if (h == 4) wait_vm_i8<NB - 1 + 4 * DPW>();
-                        else wait_vm_i8<0>();
+                        if (h == 0) vm_wait_fenced<NB - 1>();
+                        else if (h == 1) vm_wait_fenced<NB - 1 + DPW>();
+                        else if (h == 2) vm_wait_fenced<NB - 1 + 2 * DPW>();
+                        else if (h == 3) vm_wait_fenced<NB - 1 + 3 * DPW>();
+                        else if (h == 4) vm_wait_fenced<NB - 1 + 4 * DPW>();
+                        else vm_wait_fenced<0>();
                     }
 #pragma unroll
                     for (int tm = 0; tm < 4; ++tm)
@@ -600,8 +578,8 @@ __device__ __forceinline__ void g8_sweep(const g8_ctx& c, int plane0, i32x16 (&a
         if (UP > 3 && pc + 2 < c.cntp) pair(pc, std::integral_constant<int, 2>{});
     }
     // requests past the end (clamped, never used) are still landing: drain them while their registers are allocated
-    wait_vm_i8<0>();
-    wait_lgkm0_i8();
+    vm_wait_fenced<0>();
+    wait_lgkm0_fenced();
 #pragma unroll
     for (int f = 0; f < NB; ++f) asm volatile("" ::"v"(B[f]));
     asm volatile("" ::"v"(A[0][0]), "v"(A[0][1]), "v"(A[0][2]), "v"(A[0][3]));

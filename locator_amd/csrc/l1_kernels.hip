@@ -8,7 +8,6 @@
 
 #include "common.h"
 
-#define KT 32  // SNPs per k-tile
 #define LP 36  // LDS pitch (floats) of a [row][32 k] tile: 16-B aligned rows, conflict-free ds_read_b128
 
 // ---------------------------------------------------------------------------------------------
@@ -357,13 +356,6 @@ __global__ __launch_bounds__(256) void l1_reduce_kernel(const float* __restrict_
 // most two waves (ranges are >= NHT units), slot 0 = the wave that did unit-tile 0, slot 1 = the
 // other.  l1_gamma_beta_adam_kernel then adds the two slots in a fixed order and applies Adam.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void adam_update_fast(float& w, float& m, float& v, float g, float alpha) {
-    m = m + (g - m) * ADAM_C1;
-    v = v + (g * g - v) * ADAM_C2;
-    // v_sqrt_f32 / v_rcp_f32: 1 ulp each, i.e. < 4e-7 relative on an update that is <= lr
-    w = w - (m * alpha) * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(v) + ADAM_EPS);
-}
-
 template <int NHT, int NTM = 13, bool INDROP = false>
 __global__ __launch_bounds__(256, 2) void l1_bwd_adam_kernel(
     const uint8_t* __restrict__ X, int64_t pitch, const int32_t* __restrict__ rows, int n_b, int K, int Kp,
@@ -885,34 +877,6 @@ __global__ void l1_gamma_beta_adam_kernel(int K, const float* __restrict__ gbs, 
 // ---------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------
-template <typename F>
-static int set_max_lds(F* func, size_t bytes) {
-    if (bytes <= 64 * 1024) return 0;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(func),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) {
-        loc_set_error("hipFuncSetAttribute(%zu): %s", bytes, hipGetErrorString(e));
-        return (int)e;
-    }
-    return 0;
-}
-
-#define NHT_SWITCH(NHT_VALUE, MACRO)                                                        \
-    switch (NHT_VALUE) {                                                                    \
-        case 1: MACRO(1); break;   case 2: MACRO(2); break;   case 3: MACRO(3); break;      \
-        case 4: MACRO(4); break;   case 5: MACRO(5); break;   case 6: MACRO(6); break;      \
-        case 7: MACRO(7); break;   case 8: MACRO(8); break;   case 9: MACRO(9); break;      \
-        case 10: MACRO(10); break; case 11: MACRO(11); break; case 12: MACRO(12); break;    \
-        case 13: MACRO(13); break; case 14: MACRO(14); break; case 15: MACRO(15); break;    \
-        case 16: MACRO(16); break; case 17: MACRO(17); break; case 18: MACRO(18); break;    \
-        case 19: MACRO(19); break; case 20: MACRO(20); break; case 21: MACRO(21); break;    \
-        case 22: MACRO(22); break; case 23: MACRO(23); break; case 24: MACRO(24); break;    \
-        case 25: MACRO(25); break; case 26: MACRO(26); break; case 27: MACRO(27); break;    \
-        case 28: MACRO(28); break; case 29: MACRO(29); break; case 30: MACRO(30); break;    \
-        case 31: MACRO(31); break; case 32: MACRO(32); break;                               \
-        default: loc_set_error("%s: width %d unsupported (Hp must be 32..1024)", __func__, 32 * (NHT_VALUE)); return -1; \
-    }
-
 extern "C" int loc_bn_batch_stats(const uint8_t* X, int64_t x_pitch, const int32_t* rows, int n_b, int K, int Kp,
                                   const float* gamma, const float* beta, float* mov_mean, float* mov_var,
                                   float* out4, void* stream) {
@@ -1077,6 +1041,15 @@ static int l1_backward_main_impl(const uint8_t* X, int64_t x_pitch, const int32_
                                  float* gb_scratch, const float* alpha_tab, int alpha_tab_len,
                                  const float* lr, const int* t_base, int t_off, int grid,
                                  const loc_tuning* tune, const uint8_t* in_mask, float in_ks, void* stream) {
+    // every form of the backward kernel takes the same arguments (the 32-row kernel two more: the Dropout mask on the
+    // BatchNorm output and its scale); KERN in parentheses, since it holds template commas
+#define L1B_LAUNCH(KERN, GRID, BLOCK, LDS, ...)                                                                       \
+    {                                                                                                                 \
+        LOC_ENSURE_LDS(KERN, LDS);                                                                                    \
+        hipLaunchKernelGGL(KERN, dim3(GRID), dim3(BLOCK), LDS, (hipStream_t)stream, X, x_pitch, rows, n_b, d->K,      \
+                           d->Kp, bn4, dz1, w1s, m1s, v1s, gb_scratch, b1, m_b1, v_b1, alpha_tab, alpha_tab_len, lr,  \
+                           t_base, t_off, n_active, ##__VA_ARGS__);                                                   \
+    }
     if (in_mask && n_b > LOC_ROWS) {
         loc_set_error("loc_l1_backward_adam: dropout on the BatchNorm output (--nlayers 1) needs --batch_size <= 32");
         return -1;
@@ -1095,17 +1068,12 @@ static int l1_backward_main_impl(const uint8_t* X, int64_t x_pitch, const int32_
         // more than 128 rows: row blocks streamed from L2 (l1_bwd_adam_big_kernel)
         if (in_mask) { loc_set_error("loc_l1_backward_adam: --nlayers 1 with dropout needs --batch_size <= 32"); return -1; }
         const size_t lds_big = ((size_t)d->Hp + (size_t)(n_b + 31) / 32 * 32) * sizeof(float);
-#define LAUNCH_BWD_BIG(N)                                                                                      \
-    hipLaunchKernelGGL((l1_bwd_adam_big_kernel<N, 13>), dim3(grid), dim3(256), lds_big, (hipStream_t)stream, X, x_pitch, \
-                       rows, n_b, d->K, d->Kp, bn4, dz1, w1s, m1s, v1s, gb_scratch, b1, m_b1, v_b1,            \
-                       alpha_tab, alpha_tab_len, lr, t_base, t_off, n_active);
         switch (nht) {
-            case 2: LAUNCH_BWD_BIG(2) break;
-            case 4: LAUNCH_BWD_BIG(4) break;
-            case 8: LAUNCH_BWD_BIG(8) break;
+            case 2: L1B_LAUNCH((l1_bwd_adam_big_kernel<2, 13>), grid, 256, lds_big) break;
+            case 4: L1B_LAUNCH((l1_bwd_adam_big_kernel<4, 13>), grid, 256, lds_big) break;
+            case 8: L1B_LAUNCH((l1_bwd_adam_big_kernel<8, 13>), grid, 256, lds_big) break;
             default: loc_set_error("loc_l1_backward_adam: more than 32 rows need width 64/128/256 after padding (got %d)", d->Hp); return -1;
         }
-#undef LAUNCH_BWD_BIG
         LOC_CHECK_LAUNCH();
         return 0;
     }
@@ -1115,24 +1083,15 @@ static int l1_backward_main_impl(const uint8_t* X, int64_t x_pitch, const int32_
     // tune->l1b_rows = 1: the bf16x3 row-block kernel also for <= 32 rows (measurement / parity switch)
     if (rb == 1 && tune && tune->l1b_rows == 1 && nht == 8 && !in_mask) {
         const size_t lds = ((size_t)d->Hp * 36 + d->Hp + 32) * sizeof(float);
-        LOC_ENSURE_LDS((l1_bwd_adam_rows_kernel<8, 13, 1>), lds);
-        hipLaunchKernelGGL((l1_bwd_adam_rows_kernel<8, 13, 1>), dim3(grid), dim3(256), lds, (hipStream_t)stream, X,
-                           x_pitch, rows, n_b, d->K, d->Kp, bn4, dz1, w1s, m1s, v1s, gb_scratch, b1, m_b1, v_b1,
-                           alpha_tab, alpha_tab_len, lr, t_base, t_off, n_active);
+        L1B_LAUNCH((l1_bwd_adam_rows_kernel<8, 13, 1>), grid, 256, lds)
         LOC_CHECK_LAUNCH();
         return 0;
     }
     if (rb > 1) {
         // more than 32 rows: RB row blocks per weight tile (widths of the fused hidden stack up to 256 only).
         // RB = 2 keeps two workgroups per CU (66 KB of dz each at width 256); RB = 3, 4 run one per CU.
-#define LAUNCH_BWD_RB(N, R)                                                                                    \
-    {                                                                                                          \
-        LOC_ENSURE_LDS((l1_bwd_adam_rows_kernel<N, 13, R>), lds);                                              \
-        hipLaunchKernelGGL((l1_bwd_adam_rows_kernel<N, 13, R>), dim3(R > 2 ? (n_active + 7) / 8 : grid),         \
-                           dim3(R > 2 ? 512 : 256), lds, (hipStream_t)stream, X, x_pitch,                      \
-                           rows, n_b, d->K, d->Kp, bn4, dz1, w1s, m1s, v1s, gb_scratch, b1, m_b1, v_b1,        \
-                           alpha_tab, alpha_tab_len, lr, t_base, t_off, n_active);                             \
-    }
+#define LAUNCH_BWD_RB(N, R) \
+    L1B_LAUNCH((l1_bwd_adam_rows_kernel<N, 13, R>), R > 2 ? (n_active + 7) / 8 : grid, R > 2 ? 512 : 256, lds)
 #define LAUNCH_BWD_N(N)                                                                                        \
     switch (rb) {                                                                                              \
         case 2: LAUNCH_BWD_RB(N, 2) break;                                                                     \
@@ -1150,20 +1109,8 @@ static int l1_backward_main_impl(const uint8_t* X, int64_t x_pitch, const int32_
         LOC_CHECK_LAUNCH();
         return 0;
     }
-#define LAUNCH_BWD(N)                                                                                          \
-    {                                                                                                          \
-        LOC_ENSURE_LDS((l1_bwd_adam_kernel<N>), lds);                                                          \
-        hipLaunchKernelGGL(l1_bwd_adam_kernel<N>, dim3(grid), dim3(256), lds, (hipStream_t)stream, X, x_pitch, \
-                           rows, n_b, d->K, d->Kp, bn4, dz1, w1s, m1s, v1s, gb_scratch, b1, m_b1, v_b1,        \
-                           alpha_tab, alpha_tab_len, lr, t_base, t_off, n_active, (const uint8_t*)nullptr, 1.f); \
-    }
-#define LAUNCH_BWD_DROP(N)                                                                                     \
-    {                                                                                                          \
-        LOC_ENSURE_LDS((l1_bwd_adam_kernel<N, 13, true>), lds);                                                \
-        hipLaunchKernelGGL((l1_bwd_adam_kernel<N, 13, true>), dim3(grid), dim3(256), lds, (hipStream_t)stream, X, \
-                           x_pitch, rows, n_b, d->K, d->Kp, bn4, dz1, w1s, m1s, v1s, gb_scratch, b1, m_b1, v_b1, \
-                           alpha_tab, alpha_tab_len, lr, t_base, t_off, n_active, in_mask, in_ks);             \
-    }
+#define LAUNCH_BWD(N) L1B_LAUNCH((l1_bwd_adam_kernel<N>), grid, 256, lds, (const uint8_t*)nullptr, 1.f)
+#define LAUNCH_BWD_DROP(N) L1B_LAUNCH((l1_bwd_adam_kernel<N, 13, true>), grid, 256, lds, in_mask, in_ks)
     if (in_mask) {
         NHT_SWITCH(nht, LAUNCH_BWD_DROP)
         LOC_CHECK_LAUNCH();
@@ -1172,13 +1119,7 @@ static int l1_backward_main_impl(const uint8_t* X, int64_t x_pitch, const int32_
     // tune->l1b_nt_mask = 9 | 13 | 15 (or -1 for "nothing non-temporal") overrides the cache-policy mask NTM for
     // width 256 (measurement switch); 0 = the kernel's default
     const int ntm = !tune || tune->l1b_nt_mask == 0 ? -1 : (tune->l1b_nt_mask < 0 ? 0 : tune->l1b_nt_mask);
-#define LAUNCH_BWD_NT(M)                                                                                       \
-    {                                                                                                          \
-        LOC_ENSURE_LDS((l1_bwd_adam_kernel<8, M>), lds);                                                       \
-        hipLaunchKernelGGL((l1_bwd_adam_kernel<8, M>), dim3(grid), dim3(256), lds, (hipStream_t)stream, X, x_pitch, \
-                           rows, n_b, d->K, d->Kp, bn4, dz1, w1s, m1s, v1s, gb_scratch, b1, m_b1, v_b1,        \
-                           alpha_tab, alpha_tab_len, lr, t_base, t_off, n_active, (const uint8_t*)nullptr, 1.f); \
-    }
+#define LAUNCH_BWD_NT(M) L1B_LAUNCH((l1_bwd_adam_kernel<8, M>), grid, 256, lds, (const uint8_t*)nullptr, 1.f)
     if (nht == 8 && ntm >= 0) {
         switch (ntm) {
             case 0: LAUNCH_BWD_NT(0) break; case 9: LAUNCH_BWD_NT(9) break; case 15: LAUNCH_BWD_NT(15) break;
@@ -1189,6 +1130,8 @@ static int l1_backward_main_impl(const uint8_t* X, int64_t x_pitch, const int32_
     }
 #undef LAUNCH_BWD
 #undef LAUNCH_BWD_DROP
+#undef LAUNCH_BWD_NT
+#undef L1B_LAUNCH
     LOC_CHECK_LAUNCH();
     return 0;
 }

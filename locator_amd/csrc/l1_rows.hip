@@ -34,10 +34,6 @@
 // per-epoch validation sweep), where the conversion is used once.
 #include "common.h"
 
-
-#define KT 32
-
-__device__ __forceinline__ uint32_t rne16(uint32_t u) { return u + 0x7FFFu + ((u >> 16) & 1u); }
 __device__ __forceinline__ float lane_xor1(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
 }

@@ -24,59 +24,10 @@
 #define SF_THREADS 512
 #endif
 
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() would also drain vmcnt, i.e. wait for
-// the weight prefetch that is deliberately kept in flight across the reduction phases.  Inside
-// stack_fused_kernel no thread ever reads another thread's GLOBAL writes, so LDS ordering is all the
-// barrier has to provide ("memory" keeps the compiler from moving accesses across it).
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// Untracked loads of a worker (the compiler neither counts nor waits for them; sf_wait does).
-// 16 bytes at (wave-uniform base) + (the lane's 32-bit byte offset) + OFF.  The destination is a fresh definition ("=v").
-// That a ring register is never copied while its load is in flight follows from how the requests are placed, not from the
-// constraint: every request is unconditional (one chain of definitions per register, nothing for the compiler to merge),
-// and the readers of the old rows are ordered in front of the request (trip(): the sums pass through an asm statement),
-// so the old value is dead where the new one is defined and both get the same register.  The ISA of every instantiation
-// shows no move of a ring register; look again after any change here.
-template <int OFF>
-__device__ __forceinline__ void sf_gload16(f32x4& v, const void* base, uint32_t voff) {
-    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(v) : "v"(voff), "s"(base), "n"(OFF) : "memory");
-}
-// the base of such a request must be in scalar registers: a pointer that is the same in every lane, said so to the compiler
-__device__ __forceinline__ const float* sf_uniform(const float* p) {
-    const uint64_t u = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-    return reinterpret_cast<const float*>(((uint64_t)hi << 32) | lo);
-}
-// 4 bytes / 1 byte (zero-extended) at a per-lane address.  Several of these sit behind a condition, so the destination is an
-// in-out operand ("+v") of an initialised variable: the load overwrites the register that holds the initial value, and there
-// is no second value that a merge behind the condition could make the compiler copy while the load is in flight.
-template <class T>
-__device__ __forceinline__ void sf_gload4(T& v, const void* p) {
-    static_assert(sizeof(T) == 4, "one register");
-    asm volatile("global_load_dword %0, %1, off" : "+v"(v) : "v"(p) : "memory");
-}
-__device__ __forceinline__ void sf_gload1(uint32_t& v, const void* p) {
-    asm volatile("global_load_ubyte %0, %1, off" : "+v"(v) : "v"(p) : "memory");
-}
-// Wait until at most N vector-memory operations of the wave are outstanding.  COUNTING RULE (one counter for loads and
-// stores): loads land in order among loads, but a store may retire before an older load.  So "at most N outstanding"
-// proves that a load has landed only if N is the number of LOADS that EVERY wave issues after it: stores never count,
-// and neither do loads behind a condition.  sf_landed(x) right behind the wait ties a register that the wait protects:
-// asm volatile statements keep their order, and every use of x depends on the tie, so none can be scheduled above the
-// wait.  (-DLOC_STACK_DEBUG_DRAIN, `make debug_drain`: every hand count becomes vmcnt(0); tests compare the two builds
-// bit for bit.)
-#ifdef LOC_STACK_DEBUG_DRAIN
-#define SF_VMCNT(N) 0
-#else
-#define SF_VMCNT(N) (N)
-#endif
-template <int N>
-__device__ __forceinline__ void sf_wait() {
-    static_assert(N >= 0 && N <= 63, "vmcnt has six bits");
-    asm volatile("s_waitcnt vmcnt(%0)" : : "n"(SF_VMCNT(N)) : "memory");
-}
-template <class T>
-__device__ __forceinline__ void sf_landed(T& x) { asm volatile("" : "+v"(x)); }
+// The weight ring and every other load of a worker are untracked loads with hand-counted waits (gload16_uniform,
+// gload4_inout, gload1_inout, vm_wait, vm_wait_slot, vm_landed: common.h, with the counting rule).  The workgroup barrier is
+// lds_barrier(): inside stack_fused_kernel no thread ever reads another thread's GLOBAL writes, and __syncthreads() would
+// drain the ring.
 
 // e0^2 + e1^2 of the loss, with its roundings written out.  Left to the compiler, which product is fused into the sum is its
 // choice per instantiation, and it changes with unrelated code around it (a distance then moves by an ulp and val_loss with it).
@@ -88,15 +39,6 @@ __device__ __forceinline__ float sf_sumsq_train(float e0, float e1) {
     return b + a;
 }
 __device__ __forceinline__ float sf_sumsq_eval(float e0, float e1) { return fmaf(e1, e1, e0 * e0); }
-// the wait in front of a ring slot, with the slot's registers tied to it
-template <int N>
-__device__ __forceinline__ void sf_wait_slot(f32x4& a) {
-    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(a) : "n"(SF_VMCNT(N)) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void sf_wait_slot(f32x4& a, f32x4& b, f32x4& c, f32x4& d) {
-    asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(SF_VMCNT(N)) : "memory");
-}
 
 template <int NHT, int R, bool TRAIN>
 __global__ __launch_bounds__(SF_THREADS) void stack_fused_kernel(
@@ -162,7 +104,7 @@ __global__ __launch_bounds__(SF_THREADS) void stack_fused_kernel(
     // still adds its k ascending, so the sums are what they were.
     //
     // From the first ring request to the last epilogue every load of a worker is an untracked asm load and every wait is
-    // counted by hand (the rule is above sf_wait): a load the compiler tracks would be waited for with the ring's younger
+    // counted by hand (the rule is above vm_wait): a load the compiler tracks would be waited for with the ring's younger
     // requests, i.e. by draining the ring.  Stores stay plain: nothing waits for them.
     constexpr int RING = KPG < 32 ? KPG : 32;
     constexpr int RW = RING >= 16 ? RING / 8 : 1;      // rows per slot: 4 at widths 256 / 512, 1 at 128 (8 slots) and 64 (2)
@@ -184,11 +126,11 @@ __global__ __launch_bounds__(SF_THREADS) void stack_fused_kernel(
     auto load_slot = [&](const float* __restrict__ Wsrc, int c, int s) {
         const char* base = reinterpret_cast<const char*>(Wsrc) + (size_t)c * (RW * ROWB);
         static_assert(RW == 1 || RW == 4, "rows per slot");
-        sf_gload16<0>(ring[s * RW], base, toff[0]);
+        gload16_uniform<0>(ring[s * RW], base, toff[0]);
         if constexpr (RW == 4) {
-            sf_gload16<ROWB % 4096>(ring[s * RW + 1], base, toff[ROWB / 4096]);
-            sf_gload16<(2 * ROWB) % 4096>(ring[s * RW + 2], base, toff[2 * ROWB / 4096]);
-            sf_gload16<(3 * ROWB) % 4096>(ring[s * RW + 3], base, toff[3 * ROWB / 4096]);
+            gload16_uniform<ROWB % 4096>(ring[s * RW + 1], base, toff[ROWB / 4096]);
+            gload16_uniform<(2 * ROWB) % 4096>(ring[s * RW + 2], base, toff[2 * ROWB / 4096]);
+            gload16_uniform<(3 * ROWB) % 4096>(ring[s * RW + 3], base, toff[3 * ROWB / 4096]);
         }
     };
     auto fma_slot = [&](int c, int s, f32x4 (&acc)[R]) {
@@ -214,13 +156,13 @@ __global__ __launch_bounds__(SF_THREADS) void stack_fused_kernel(
         constexpr int N = (NS - 1) * RW + (decltype(last)::value ? NO : 0);
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-            if constexpr (RW == 4) sf_wait_slot<N>(ring[s * RW], ring[s * RW + 1], ring[s * RW + 2], ring[s * RW + 3]);
-            else sf_wait_slot<N>(ring[s * RW]);
+            if constexpr (RW == 4) vm_wait_slot<N>(ring[s * RW], ring[s * RW + 1], ring[s * RW + 2], ring[s * RW + 3]);
+            else vm_wait_slot<N>(ring[s * RW]);
             fma_slot(c0 + s, s, acc);
             // the slot's last use comes before its request: the sums pass through an asm statement in front of it, or the
             // compiler would let the FMAs trail the request and keep the old rows in a copy taken before they landed
 #pragma unroll
-            for (int r = 0; r < R; ++r) sf_landed(acc[r]);
+            for (int r = 0; r < R; ++r) vm_landed(acc[r]);
             load_slot(Wn, cn + s, s);
         }
     };
@@ -241,9 +183,9 @@ __global__ __launch_bounds__(SF_THREADS) void stack_fused_kernel(
     // Behind the last pass the ring's requests are dummies that nobody consumes; they may land until the wave ends, so
     // their registers must not be handed to anything else before: ring_end() keeps them the ring's up to that point.
     auto ring_end = [&]() {
-        sf_wait<0>();
+        vm_wait<0>();
 #pragma unroll
-        for (int k = 0; k < RING; ++k) sf_landed(ring[k]);
+        for (int k = 0; k < RING; ++k) vm_landed(ring[k]);
     };
     // weight matrix of pass p: forward layers 2..L use Wh[0..L-2]; backward L..2 use WhT[L-2..0]
     const int n_pass = TRAIN ? 2 * (L - 1) : (L - 1);
@@ -251,8 +193,8 @@ __global__ __launch_bounds__(SF_THREADS) void stack_fused_kernel(
         // The dummy behind the last pass is the first RING rows of every k-group of Wh[0]: rows kq * KPG + j < Hp of the
         // first hidden kernel, which exists at every width since L >= 2.  Every other request is a row of the matrix of
         // a pass that runs.  So every address of the stream lies inside Wh or WhT.
-        if (p >= n_pass) return sf_uniform(Wh);
-        return sf_uniform(p < L - 1 ? Wh + (int64_t)p * HH : WhT + (int64_t)(2 * (L - 1) - 1 - p) * HH);
+        if (p >= n_pass) return uniform_ptr(Wh);
+        return uniform_ptr(p < L - 1 ? Wh + (int64_t)p * HH : WhT + (int64_t)(2 * (L - 1) - 1 - p) * HH);
     };
     auto ring_start = [&]() {
         const float* W0 = wseq(0);
@@ -317,26 +259,26 @@ __global__ __launch_bounds__(SF_THREADS) void stack_fused_kernel(
         for (int o = 0; o < NO; ++o) {
             const int i = t + SF_THREADS * o;
             a1v[o] = 0.f;
-            if (stage && i < R * Hp) sf_gload4(a1v[o], a1_in + (int64_t)(r0 + i / Hp) * Hp + i % Hp);
+            if (stage && i < R * Hp) gload4_inout(a1v[o], a1_in + (int64_t)(r0 + i / Hp) * Hp + i % Hp);
         }
-        if (has_y) sf_gload4(yrow, rows + r0 + t);
-        sf_gload4(h_wa0, wa + 2 * (t % Hp));
-        sf_gload4(h_wa1, wa + 2 * (t % Hp) + 1);
+        if (has_y) gload4_inout(yrow, rows + r0 + t);
+        gload4_inout(h_wa0, wa + 2 * (t % Hp));
+        gload4_inout(h_wa1, wa + 2 * (t % Hp) + 1);
         if (t < R) {
-            sf_gload4(h_ba0, ba); sf_gload4(h_ba1, ba + 1);
-            sf_gload4(h_w00, wb); sf_gload4(h_w01, wb + 1); sf_gload4(h_w10, wb + 2); sf_gload4(h_w11, wb + 3);
-            sf_gload4(h_bb0, bb); sf_gload4(h_bb1, bb + 1);
+            gload4_inout(h_ba0, ba); gload4_inout(h_ba1, ba + 1);
+            gload4_inout(h_w00, wb); gload4_inout(h_w01, wb + 1); gload4_inout(h_w10, wb + 2); gload4_inout(h_w11, wb + 3);
+            gload4_inout(h_bb0, bb); gload4_inout(h_bb1, bb + 1);
         }
         ring_start();
-        sf_wait<RING>();
+        vm_wait<RING>();
 #pragma unroll
-        for (int o = 0; o < NO; ++o) sf_landed(a1v[o]);
-        sf_landed(yrow);
-        sf_landed(h_wa0); sf_landed(h_wa1);
-        sf_landed(h_ba0); sf_landed(h_ba1); sf_landed(h_w00); sf_landed(h_w01); sf_landed(h_w10); sf_landed(h_w11);
-        sf_landed(h_bb0); sf_landed(h_bb1);
+        for (int o = 0; o < NO; ++o) vm_landed(a1v[o]);
+        vm_landed(yrow);
+        vm_landed(h_wa0); vm_landed(h_wa1);
+        vm_landed(h_ba0); vm_landed(h_ba1); vm_landed(h_w00); vm_landed(h_w01); vm_landed(h_w10); vm_landed(h_w11);
+        vm_landed(h_bb0); vm_landed(h_bb1);
         // the labels of this block's rows: younger than the ring's first requests, landed with the first pass's operands
-        if (has_y) { sf_gload4(h_y0, Y + (int64_t)(int32_t)yrow * 2); sf_gload4(h_y1, Y + (int64_t)(int32_t)yrow * 2 + 1); }
+        if (has_y) { gload4_inout(h_y0, Y + (int64_t)(int32_t)yrow * 2); gload4_inout(h_y1, Y + (int64_t)(int32_t)yrow * 2 + 1); }
 #pragma unroll
         for (int o = 0; o < NO; ++o) {
             const int i = t + SF_THREADS * o;
@@ -356,16 +298,16 @@ __global__ __launch_bounds__(SF_THREADS) void stack_fused_kernel(
             for (int o = 0; o < NO; ++o) {
                 const int i = (t + SF_THREADS * o) % (R * Hp);
                 e_bias[o] = 0.f;
-                sf_gload4(e_bias[o], bias + i % Hp);
+                gload4_inout(e_bias[o], bias + i % Hp);
                 e_m[o] = 1;
-                if (dr) sf_gload1(e_m[o], mask + (int64_t)(r0 + i / Hp) * Hp + i % Hp);
+                if (dr) gload1_inout(e_m[o], mask + (int64_t)(r0 + i / Hp) * Hp + i % Hp);
             }
         });
         lds_barrier();
-        sf_wait<RING>();        // the epilogue's operands: RING requests are younger
+        vm_wait<RING>();        // the epilogue's operands: RING requests are younger
 #pragma unroll
-        for (int o = 0; o < NO; ++o) { sf_landed(e_bias[o]); sf_landed(e_m[o]); }
-        sf_landed(h_y0); sf_landed(h_y1);
+        for (int o = 0; o < NO; ++o) { vm_landed(e_bias[o]); vm_landed(e_m[o]); }
+        vm_landed(h_y0); vm_landed(h_y1);
         float* aout = acts + (int64_t)(l - 1) * blk;
 #pragma unroll
         for (int o = 0; o < NO; ++o) {
@@ -463,15 +405,15 @@ __global__ __launch_bounds__(SF_THREADS) void stack_fused_kernel(
                 const int i = (t + SF_THREADS * o) % (R * Hp);
                 const int64_t gi = (int64_t)(r0 + i / Hp) * Hp + i % Hp;
                 e_a[o] = 0.f;
-                sf_gload4(e_a[o], aprev + gi);
+                gload4_inout(e_a[o], aprev + gi);
                 e_m[o] = 1;
-                if (dr) sf_gload1(e_m[o], mask + gi);
+                if (dr) gload1_inout(e_m[o], mask + gi);
             }
         });
         lds_barrier();
-        sf_wait<RING>();        // the epilogue's operands: RING requests are younger
+        vm_wait<RING>();        // the epilogue's operands: RING requests are younger
 #pragma unroll
-        for (int o = 0; o < NO; ++o) { sf_landed(e_a[o]); sf_landed(e_m[o]); }
+        for (int o = 0; o < NO; ++o) { vm_landed(e_a[o]); vm_landed(e_m[o]); }
         float* dzo = dz + (int64_t)(l - 2) * blk;
 #pragma unroll
         for (int o = 0; o < NO; ++o) {

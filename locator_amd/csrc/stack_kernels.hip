@@ -336,34 +336,6 @@ __global__ __launch_bounds__(256) void head_eval_kernel(const float* __restrict_
 // ---------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------
-template <typename F>
-static int set_max_lds2(F* func, size_t bytes) {
-    if (bytes <= 64 * 1024) return 0;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(func),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) {
-        loc_set_error("hipFuncSetAttribute(%zu): %s", bytes, hipGetErrorString(e));
-        return (int)e;
-    }
-    return 0;
-}
-
-#define NHT_SWITCH(NHT_VALUE, MACRO)                                                        \
-    switch (NHT_VALUE) {                                                                    \
-        case 1: MACRO(1); break;   case 2: MACRO(2); break;   case 3: MACRO(3); break;      \
-        case 4: MACRO(4); break;   case 5: MACRO(5); break;   case 6: MACRO(6); break;      \
-        case 7: MACRO(7); break;   case 8: MACRO(8); break;   case 9: MACRO(9); break;      \
-        case 10: MACRO(10); break; case 11: MACRO(11); break; case 12: MACRO(12); break;    \
-        case 13: MACRO(13); break; case 14: MACRO(14); break; case 15: MACRO(15); break;    \
-        case 16: MACRO(16); break; case 17: MACRO(17); break; case 18: MACRO(18); break;    \
-        case 19: MACRO(19); break; case 20: MACRO(20); break; case 21: MACRO(21); break;    \
-        case 22: MACRO(22); break; case 23: MACRO(23); break; case 24: MACRO(24); break;    \
-        case 25: MACRO(25); break; case 26: MACRO(26); break; case 27: MACRO(27); break;    \
-        case 28: MACRO(28); break; case 29: MACRO(29); break; case 30: MACRO(30); break;    \
-        case 31: MACRO(31); break; case 32: MACRO(32); break;                               \
-        default: loc_set_error("%s: width %d unsupported (Hp must be 32..1024)", __func__, 32 * (NHT_VALUE)); return -1; \
-    }
-
 extern "C" int loc_dense_forward(const float* in, const float* W, const float* b, int Hp, float* out,
                                  float* out_drop, const uint8_t* mask, float keep_scale, void* stream) {
     const int nht = Hp / 32;

@@ -41,8 +41,6 @@ extern "C" int loc_debug_sr_stamps(unsigned long long* out) {
 #define SR_STAMP(i)
 #endif
 
-__device__ __forceinline__ void sr_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 __global__ __launch_bounds__(512) void stack_rows_eval_kernel(
     const float* __restrict__ a1, const float* __restrict__ rd_partial, int rd_G, int64_t rd_MH,
     const float* __restrict__ rd_cvec8, const float* __restrict__ rd_b1, const float* __restrict__ Wh,
@@ -170,7 +168,7 @@ __global__ __launch_bounds__(512) void stack_rows_eval_kernel(
         for (int r = 0; r < 16; ++r) out[rowmap(r, hi) * P + 32 * w + jl] = elu_f(acc[r] + bias);
         cur ^= 1;
         SR_STAMP(4 * (l - 2) + 2)
-        sr_lds_barrier();
+        lds_barrier();
         SR_STAMP(4 * (l - 2) + 3)
     }
     asm volatile("" ::"v"(bA[0]), "v"(bB[0]), "v"(g[0]));
@@ -190,7 +188,7 @@ __global__ __launch_bounds__(512) void stack_rows_eval_kernel(
             for (int o = 1; o < 32; o <<= 1) { p0 += __shfl_xor(p0, o); p1 += __shfl_xor(p1, o); }
             if (jl == 0) { hp[w][row][0] = p0; hp[w][row][1] = p1; }
         }
-        sr_lds_barrier();
+        lds_barrier();
         if (t < SR_ROWS) {
             const int b = r0 + t;
             if (b < n_b) {
@@ -372,7 +370,7 @@ __global__ __launch_bounds__(512, CS == 4 ? 2 : 1) void stack_rows16_eval_kernel
         }
         cur ^= 1;
         SR_STAMP(4 * (l - 2) + 2)
-        sr_lds_barrier();
+        lds_barrier();
         SR_STAMP(4 * (l - 2) + 3)
     }
     asm volatile("" ::"v"(bA[0]), "v"(bB[0]), "v"(g[0][0]), "v"(g[1][0]), "v"(g[2][0]), "v"(g[3][0]));
@@ -392,7 +390,7 @@ __global__ __launch_bounds__(512, CS == 4 ? 2 : 1) void stack_rows16_eval_kernel
             for (int o = 1; o < 32; o <<= 1) { p0 += __shfl_xor(p0, o); p1 += __shfl_xor(p1, o); }
             if (jl == 0) { hp[w][row][0] = p0; hp[w][row][1] = p1; }
         }
-        sr_lds_barrier();
+        lds_barrier();
         if (t < R) {
             const int b = r0 + t;
             if (b < n_b) {

@@ -159,14 +159,28 @@ def test_no_instruction_touches_an_untracked_load_destination_before_the_hand_co
     assert any("vmcnt(0)" in t for t in after), "no drain of the untracked loads after the loop"
 
 
+# hand-counted waits the walk must meet per kernel (8 unless listed): a floor that only proves the walker found the loop
+_MIN_WAITS = {"stack_fused.hip": 4}
+
+
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 @pytest.mark.parametrize("source,pattern,n_kernels", [("l1_gemm_i8.hip", r"^_Z17l1_gemm_i8_kernelILi", 6),
-                                                      ("l1_gemm.hip", r"^_Z14l1_gemm_kernelILi", 3)])
+                                                      ("l1_gemm.hip", r"^_Z14l1_gemm_kernelILi", 3),
+                                                      ("stack_fused.hip", r"stack_fused_kernel", 18)])
 def test_large_m_gemm_kernels_keep_their_untracked_fragment_loads_untouched_until_counted(source, pattern, n_kernels):
     """The same property for the hand-counted weight-fragment loads of the many-row layer-1 GEMMs (l1_gemm_i8.hip,
-    l1_gemm.hip): every instantiation the library launches."""
+    l1_gemm.hip) and for the register ring of the fused hidden stack (stack_fused.hip): every instantiation the library
+    launches.
+
+    What the model is, and is not.  It is LINEAR: the prologue, then the main loop (the backward branch spanning the most
+    untracked loads) taken twice; other branches are walked straight through.  A load behind a branch is therefore counted
+    as issued, where stack_fused.hip's own counting rule is the opposite (a conditional load never counts, because not every
+    wave issues it).  So this is a check on REGISTER REUSE - no compiler-generated instruction names the destination of an
+    untracked load that the model still holds in flight - and not a proof of the counts; the drained twin library
+    (`make debug_drain`, compared bit for bit by the GPU tests) remains that.  The floors below (16 loads, and 8 waits or
+    4 for the ring) only prove that the walker found the loop."""
     ks = _kernels(source, pattern)
     assert len(ks) == n_kernels, sorted(ks)
     for name, lines in ks.items():
         prog, lo, hi, n_loads, n_waits = _walk(lines)
-        assert n_loads >= 16 and n_waits >= 8, (name, n_loads, n_waits)
+        assert n_loads >= 16 and n_waits >= _MIN_WAITS.get(source, 8), (name, n_loads, n_waits)
