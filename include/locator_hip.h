@@ -644,6 +644,7 @@ int loc_dosage_rows(const float* ds, int64_t n_variants, int n_samples, const ui
 int loc_query_rows(const int8_t* gt, int64_t n_variants, int n_samples, int ploidy, const int32_t* col_variant,
                    const int8_t* col_allele, int K, const int32_t* sample_order, int n_out, uint8_t* X, int64_t x_pitch,
                    void* stream);
+/* The --dosage form of loc_query_rows, for float dosages, is declared in include/locator_hip_query.h. */
 
 /* ---- per-SNP attribution of a kept model (python -m locator_amd.explain; DESIGN.md §8, the explain command) ----
  * loc_explain_stack_grad: a1 = layer 1's ELU output [n][Hp] (loc_l1_forward_rows / loc_l1_forward, exact form); wh / bh / wa / wb

@@ -1,6 +1,7 @@
 """The C ABI as include/locator_hip.h declares it, read once at import: the LOC_* constants as module attributes, the
 structs as ctypes Structures (STRUCTS) and the prototypes as (restype, argtypes) pairs (PROTOTYPES).  Nothing else in the
-package restates the header.  No torch here: locator_amd.genotypes and the command line import this module before torch.
+package restates the header.  include/locator_hip_query.h (later entry points) is read likewise: EXT_PROTOTYPES.  No
+torch here: locator_amd.genotypes and the command line import this module before torch.
 
 The reader knows the header's spelling, not C: one declaration per `;`, scalar types from _SCALARS, comments only as
 /* */.  Anything else raises with the offending text, so that a header edit cannot silently drop or mis-type an entry."""
@@ -9,6 +10,9 @@ import os
 import re
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "locator_hip.h")
+# entry points added after version 1 of the ABI (the prototype list of locator_hip.h, which tests/test_abi.py pins): the same
+# spelling, read by the same parser into EXT_PROTOTYPES; it declares functions only
+EXT_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_query.h")
 
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
             "float": C.c_float, "double": C.c_double}
@@ -91,3 +95,9 @@ if not os.path.exists(HEADER):
 with open(HEADER) as _f:
     CONSTANTS, STRUCTS, PROTOTYPES = parse(_f.read())
 globals().update(CONSTANTS)
+if not os.path.exists(EXT_HEADER):
+    raise FileNotFoundError(f"{EXT_HEADER} not found: it declares the entry points added after include/locator_hip.h")
+with open(EXT_HEADER) as _f:
+    _consts, _structs, EXT_PROTOTYPES = parse(_f.read())
+if _consts or _structs or set(EXT_PROTOTYPES) & set(PROTOTYPES):
+    raise ValueError(f"{EXT_HEADER} may declare new functions only")

@@ -43,6 +43,15 @@ __device__ __forceinline__ float elu_f(float z) { return z > 0.f ? z : expm1f(z)
 // ELU'(z) from the activation value a = ELU(z):  1 if z > 0 else e^z = a + 1
 __device__ __forceinline__ float elu_grad_from_act(float a) { return a > 0.f ? 1.f : a + 1.f; }
 
+// --dosage: the fixed-point form of a float dosage, q = rint(fp32(d) * 63) clamped to 0..126, -1 for NaN
+// (missing).  A single fp32 product and a rounding - nothing for contraction to fuse - so it agrees bit for bit with
+// genotypes.dosage_q.  ONE home: filter_kernels.hip (training windows) and query_kernels.hip (a kept model's query).
+__device__ __forceinline__ int dosage_q_dev(float d) {
+    if (d != d) return -1;                           // NaN: missing
+    const float f = fminf(fmaxf(rintf(d * (float)LOC_DOSAGE_UNIT), 0.f), (float)(2 * LOC_DOSAGE_UNIT));
+    return (int)f;
+}
+
 // Keras Adam: eps outside the root, bias correction folded into alpha.
 __device__ __forceinline__ void adam_update(float& w, float& m, float& v, float g, float alpha) {
     m = m + (g - m) * ADAM_C1;

@@ -149,12 +149,7 @@ extern "C" int loc_filter_snps_rows(const int8_t* gt, int64_t n_variants, int n_
 // (genotypes.dosage_q is the host form).  A single product and a rounding - nothing for fp32 contraction to fuse - so the
 // device and the NumPy form agree bit for bit.  Filter (genotypes.filter_dosage): over the called samples,
 // S = sum(q) >= 63 * min_mac, S > 0 and S < 126 * n_called (not monomorphic).  All offsets into the slice are 64-bit:
-// a 720k-variant window of 765 samples is 2.2 GB.
-__device__ __forceinline__ int dosage_q_dev(float d) {
-    if (d != d) return -1;                           // NaN: missing
-    const float f = fminf(fmaxf(rintf(d * (float)LOC_DOSAGE_UNIT), 0.f), (float)(2 * LOC_DOSAGE_UNIT));
-    return (int)f;
-}
+// a 720k-variant window of 765 samples is 2.2 GB.  dosage_q_dev: common.h (query_kernels.hip quantises with it too).
 
 // One wave per variant, lanes over the samples (64 consecutive floats per load instruction).
 __global__ __launch_bounds__(256) void dosage_flags_kernel(const float* __restrict__ ds, int64_t n_variants, int n_samples,

@@ -9,6 +9,8 @@ A = J (x_nk - mov_mean_k).  Per site, means over the rows: mean_abs_x = |A_x|, m
 sqrt(A_x^2 + A_y^2), rms_grad = sqrt(mean(J_x^2 + J_y^2)).  Sites are matched, refused and imputed exactly as predict does
 (locator_amd/query.py); the columns of a site listed more than once (a bootstrap model) are summed into one first-layer row
 before the contraction; a site absent from the query has gamma = 0, hence all four statistics 0 (present = 0).
+With --dosage the query is read as expected alt-allele dosages (FORMAT/DS, or GP; as predict --dosage) and the input is the
+dosage d = q / 63 of the fixed-point rows: J = d(x^, y^) / d d per allele copy, A = J (d - mov_mean).
 Outputs, each written atomically:
   {out}_snp_importance.txt   (several models: {out}_{model stem}_snp_importance.txt each)
   {out}_window_importance.txt with --window_size (several models: {out}_{model stem}_window_importance.txt each)
@@ -43,6 +45,9 @@ def build_parser():
                    help="missing calls at matched sites: Binomial(ploidy, training allele frequency) instead of 0")
     p.add_argument("--seed", default=None, type=int, help="NumPy seed of the --impute_missing draws")
     p.add_argument("--gpu_number", default=None, type=str, help="run on this GPU index")
+    p.add_argument("--dosage", default=None, nargs="?", const="DS", choices=("DS", "GP"),
+                   help="read the query as expected alt-allele dosages instead of GT calls: FORMAT/DS (bare --dosage; "
+                        "calldata/DS of a zarr store, float values of a --matrix) or FORMAT/GP as GP1 + 2 GP2 (VCF only)")
     p.add_argument("--window_size", default=0, type=int,
                    help="also write per-window sums of the site statistics, windows of this many bp (default 0: none)")
     p.add_argument("--top", default=10, type=int, help="sites printed to the terminal, by mean_dist (default 10)")
@@ -133,9 +138,11 @@ def window_table(chrom, pos, present, stats, size):
 
 
 # ------------------------------------------------------------------ device
-def _l1_forward(model, X, device):
+def _l1_forward(model, X, device, unit=1):
     """Layer 1's ELU output for every row of X (uint8 [n][Kp]) in the exact fp32 forms: loc_l1_forward_rows with 3 bf16
-    pieces where the LDS allows it, else the 32-row loc_l1_forward.  -> (net, a1 [ceil(n/128)*128][Hp])."""
+    pieces where the LDS allows it, else the 32-row loc_l1_forward.  unit: the fixed-point unit of X (63 for the q rows of a
+    --dosage query: import_params then holds the moving statistics in q units, and scale / shift of q give BN(d)).
+    -> (net, a1 [ceil(n/128)*128][Hp])."""
     import ctypes as C
 
     import torch
@@ -145,7 +152,8 @@ def _l1_forward(model, X, device):
     lib = _lib.load()
     n = int(X.shape[0])
     Y = torch.zeros((n, 2), dtype=torch.float32, device=device)
-    net = LocatorNet(X, Y, model["K"], model["width"], model["nlayers"], 0.0, seed=0, device=device)
+    net = LocatorNet(X, Y, model["K"], model["width"], model["nlayers"], 0.0, seed=0, device=device,
+                     **({"unit": int(unit)} if unit != 1 else {}))
     net.import_params(model["weights_used"])
     d, lay, P = net.d, net.lay, net.params.data_ptr()
     Hp, Kp = d.Hp, d.Kp
@@ -176,15 +184,16 @@ def _l1_forward(model, X, device):
     return net, a1
 
 
-def device_delta1(model, X, device="cuda:0"):
-    """loc_explain_stack_grad on the query rows X (uint8 [n][Kp], model columns) -> (net, delta1 device [2n][Hp])."""
+def device_delta1(model, X, device="cuda:0", unit=1):
+    """loc_explain_stack_grad on the query rows X (uint8 [n][Kp], model columns; in units of 1 / unit) -> (net, delta1 device
+    [2n][Hp])."""
     import torch
 
     from . import _lib
     from .net import _ptr, _stream
     lib = _lib.load()
     n = int(X.shape[0])
-    net, a1 = _l1_forward(model, X, device)
+    net, a1 = _l1_forward(model, X, device, unit)
     d, lay, P = net.d, net.lay, net.params.data_ptr()
     Hp, L = d.Hp, d.L
     _, sdlong, _, sdlat = model["locs_norm"]
@@ -221,18 +230,26 @@ def device_sites(delta1, n, U, Xs, mov_mean_sites, device="cuda:0"):
     return out.cpu().numpy()
 
 
-def explain_model(model, calls_dev, cv, ca, rows, device="cuda:0"):
-    """The four statistics (4, Ks) of one model on the query rows, plus its site index (col_site, first)."""
+def explain_model(model, calls_dev, cv, ca, rows, device="cuda:0", dosage=False):
+    """The four statistics (4, Ks) of one model on the query rows, plus its site index (col_site, first).  dosage: calls_dev
+    holds float dosages (U, N) and the rows are q = rint(63 d).  loc_explain_sites then gets everything in q units - U / 63
+    (the Jacobian per q), Xs and the moving means times 63 - so that A = (J / 63) (q - 63 mov_mean) = J (d - mov_mean) comes
+    out as it is, and rms_grad, which it returns per q, is multiplied by 63 here."""
+    from . import genotypes as G
     from . import query as Q
     col_site, first = site_index(model)
     Ks = len(first)
-    X = Q.query_rows(calls_dev, cv, ca, rows, model["K"])
-    net, delta1 = device_delta1(model, X, device)
+    unit = G.DOSAGE_UNIT if dosage else 1
+    build = Q.query_rows_dosage if dosage else Q.query_rows
+    X = build(calls_dev, cv, ca, rows, model["K"])
+    net, delta1 = device_delta1(model, X, device, unit)
     del net
-    Xs = X if Ks == model["K"] and (first == np.arange(Ks)).all() else Q.query_rows(calls_dev, cv[first], ca[first], rows, Ks)
+    Xs = X if Ks == model["K"] and (first == np.arange(Ks)).all() else build(calls_dev, cv[first], ca[first], rows, Ks)
     p = model["weights_used"]
-    U = fold_first_layer(p, col_site, Ks).astype(np.float32)
-    stats = device_sites(delta1, len(rows), U, Xs, np.asarray(p["mov_mean"], np.float64)[first], device)
+    U = (fold_first_layer(p, col_site, Ks) / unit).astype(np.float32)
+    stats = device_sites(delta1, len(rows), U, Xs, np.asarray(p["mov_mean"], np.float64)[first] * unit, device)
+    if dosage:
+        stats[3] *= unit
     return stats, col_site, first
 
 
@@ -285,21 +302,25 @@ def main(argv=None):
         for m in models:
             if is_matrix_model(m):
                 raise Q.QueryRefused(f"--window_size: {m['path']} is a --matrix model; its sites have no positions")
-    query = Q.read_query(a.vcf, a.zarr, a.matrix)
+    dosage = a.dosage is not None
+    query = Q.read_query_dosage(a.vcf, a.zarr, a.matrix, a.dosage) if dosage else Q.read_query(a.vcf, a.zarr, a.matrix)
     columns = []
     for m in models:
         cv, ca, rep = Q.match_sites(m, query)
-        Q.check_query(m, query, rep, a.min_site_overlap)
+        (Q.check_query_dosage if dosage else Q.check_query)(m, query, rep, a.min_site_overlap)
         columns.append((cv, ca))
     phased = models[0]["phased"]
     idx = Q.select_samples(query, _read_ids(a.samples) if a.samples else None)
     rows = ((2 * idx[:, None] + np.arange(2)).reshape(-1) if phased else idx).astype(np.int32)
     if not len(rows):
         raise Q.QueryRefused("no samples to explain")
-    calls, remapped, _ = Q.compact_calls(query, columns)
+    calls, remapped, _ = (Q.compact_dosages if dosage else Q.compact_calls)(query, columns)
     if a.impute_missing:
-        Q.impute_calls(calls, rows, np.concatenate(remapped), np.concatenate([ca for _, ca in columns]),
-                       np.concatenate([m["af"] for m in models]), phased)
+        every = (np.concatenate(remapped), np.concatenate([ca for _, ca in columns]), np.concatenate([m["af"] for m in models]))
+        if dosage:
+            Q.impute_dosages(calls, rows, *every)
+        else:
+            Q.impute_calls(calls, rows, *every, phased)
     for m, (cv, _) in zip(models, columns):
         m["weights_used"] = Q.absent_gamma(m["weights"], cv)
 
@@ -314,7 +335,7 @@ def main(argv=None):
         U_, N_, P_ = calls.shape
         calls_dev = calls_dev.view(U_, N_ * P_, 1)
     for m, cv, (cv_q, ca) in zip(models, remapped, columns):
-        stats, col_site, first = explain_model(m, calls_dev, cv, ca, rows, dev)
+        stats, col_site, first = explain_model(m, calls_dev, cv, ca, rows, dev, dosage)
         present = cv_q[first] >= 0
         counts = np.bincount(col_site, minlength=len(first))
         one = len(models) == 1

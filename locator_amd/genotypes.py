@@ -636,16 +636,19 @@ def _dosage_value(tok, field):
     return float(gp[1]) + 2.0 * float(gp[2])
 
 
-def read_vcf_dosage(path, field="DS"):
+def read_vcf_dosage(path, field="DS", sites=False):
     """--dosage: the expected alt-allele dosage of every call from FORMAT/DS, or from FORMAT/GP as GP1 + 2 GP2, at the field's
     position in each record's FORMAT (which may differ from record to record).  '.' = missing (NaN).  Records with more than
     one ALT allele are dropped (their number is returned as 'multiallelic_dropped').  A record without the field, or a value
     outside [-0.001, 2.001], raises ValueError naming the record and the sample; values are clamped to [0, 2] after that check.
-    Returns {'calldata/DS': float32 (variants, samples), 'samples', 'variants/POS', 'multiallelic_dropped'}."""
+    Returns {'calldata/DS': float32 (variants, samples), 'samples', 'variants/POS', 'multiallelic_dropped'}.  sites=True
+    (locator_amd.predict --dosage) adds 'variants/CHROM', 'variants/REF' and 'variants/ALT' (object arrays of str, one entry
+    per kept record; ALT '' where the record has none)."""
     if field not in ("DS", "GP"):
         raise ValueError(f"--dosage takes DS or GP (got {field!r})")
     opener = gzip.open if str(path).endswith(".gz") else open
     samples, rows, pos = None, [], []
+    chrom, ref, alt = [], [], []
     dropped = 0
     with opener(path, "rt") as fh:
         for line in fh:
@@ -681,11 +684,20 @@ def read_vcf_dosage(path, field="DS"):
                                  f"{field} is outside [{DOSAGE_LO}, {DOSAGE_HI}]")
             rows.append(np.clip(vals, 0.0, 2.0).astype(np.float32))
             pos.append(int(f[1]))
+            if sites:
+                chrom.append(f[0])
+                ref.append(f[3])
+                alt.append("" if f[4] == "." else f[4])
     if samples is None:
         raise ValueError(f"{path}: no #CHROM header line")
     ds = np.stack(rows, axis=0) if rows else np.zeros((0, len(samples)), np.float32)
-    return {"calldata/DS": ds, "samples": samples, "variants/POS": np.asarray(pos, dtype=np.int32),
-            "multiallelic_dropped": dropped}
+    out = {"calldata/DS": ds, "samples": samples, "variants/POS": np.asarray(pos, dtype=np.int32),
+           "multiallelic_dropped": dropped}
+    if sites:
+        out["variants/CHROM"] = np.array(chrom, dtype=object)
+        out["variants/REF"] = np.array(ref, dtype=object)
+        out["variants/ALT"] = np.array(alt, dtype=object)
+    return out
 
 
 def read_matrix_dosage(path):
@@ -710,7 +722,7 @@ def check_dosage(d, where):
 
 def dosage_q(d):
     """Fixed-point dosages: q = rint(fp32(d) * 63) clamped to 0..126, Q_MISSING where d is NaN; uint8 of d's shape.  The
-    device's form (csrc/filter_kernels.hip, dosage_q_dev) makes the same single fp32 product and rounding."""
+    device's form (csrc/common.h, dosage_q_dev) makes the same single fp32 product and rounding."""
     d = np.asarray(d, dtype=np.float32)
     q = np.clip(np.rint(d * np.float32(DOSAGE_UNIT)), 0, 2 * DOSAGE_UNIT)
     out = np.where(np.isnan(d), Q_MISSING, q).astype(np.uint8)

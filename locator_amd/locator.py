@@ -257,7 +257,8 @@ def _dosage_preflight():
         raise SystemExit("--dosage cannot be combined with --predict_packed: the 2-bit packed matrix holds values 0..3, "
                          "dosages are stored as 0..126")
     if _keep_model():
-        raise SystemExit("--dosage cannot be combined with --keep_model: kept models query hard calls only")
+        raise SystemExit("--dosage cannot be combined with --keep_model: keeping a dosage-trained model is not built (a model kept "
+                         "from GT calls takes dosage queries: python -m locator_amd.predict --dosage)")
     if args.zarr is not None:
         if field != "DS":
             raise SystemExit("--dosage GP: a zarr store is read from calldata/DS only; use --dosage DS")

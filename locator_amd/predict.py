@@ -3,10 +3,13 @@
 
   python -m locator_amd.predict --model out/run.model.npz --vcf new.vcf.gz --out out/new
   python -m locator_amd.predict --model out/boot_dir --zarr new.zarr --samples ids.txt --out out/new
+  python -m locator_amd.predict --model out/run.model.npz --vcf imputed.vcf.gz --dosage --out out/new     (FORMAT/DS; GP: --dosage GP)
 
 Every model's sites are matched to the query on the host (locator_amd/query.py); everything that can be
 refused is refused before any device work.  The calls of the matched variants go to the device once; every model of the
-set builds its own rows from that copy (loc_query_rows) and predicts them.  Outputs, each written atomically:
+set builds its own rows from that copy (loc_query_rows) and predicts them.  With --dosage the query is read as expected
+alt-allele dosages (imputed or low-coverage samples); the rows are built in the fixed-point unit q = rint(63 d)
+(loc_query_rows_dosage) and the model runs on d = q / 63.  Outputs, each written atomically:
   one model:     {out}_predlocs.txt
   several:       {out}_{model stem}_predlocs.txt each, and {out}_centroids.txt (what `python -m locator_amd.summarize`
                  computes over those files)
@@ -39,6 +42,9 @@ def build_parser():
                    help="missing calls at matched sites: Binomial(ploidy, training allele frequency) instead of 0")
     p.add_argument("--seed", default=None, type=int, help="NumPy seed of the --impute_missing draws")
     p.add_argument("--gpu_number", default=None, type=str, help="run on this GPU index")
+    p.add_argument("--dosage", default=None, nargs="?", const="DS", choices=("DS", "GP"),
+                   help="read the query as expected alt-allele dosages instead of GT calls: FORMAT/DS (bare --dosage; "
+                        "calldata/DS of a zarr store, float values of a --matrix) or FORMAT/GP as GP1 + 2 GP2 (VCF only)")
     p.add_argument("--predict_mode", default="auto", choices=("auto", "exact", "fast"),
                    help="first-layer arithmetic of many-row predictions (as the training command's flag)")
     p.add_argument("--predict_pieces", default=None, type=int, help="as the training command's flag")
@@ -73,6 +79,7 @@ def main(argv=None):
             os.environ[var] = a.gpu_number
     if a.seed is not None:
         np.random.seed(a.seed)
+    from . import genotypes as G
     from . import query as Q
     from .locator import _to_map_units, _write_atomic, predict_settings, write_predlocs
 
@@ -83,11 +90,12 @@ def main(argv=None):
     stems = [m["stem"] for m in models]
     if len(set(stems)) != len(stems):
         raise Q.QueryRefused("--model: two model files share the name stem " + repr(sorted(s for s in stems if stems.count(s) > 1)[0]))
-    query = Q.read_query(a.vcf, a.zarr, a.matrix)
+    dosage = a.dosage is not None
+    query = Q.read_query_dosage(a.vcf, a.zarr, a.matrix, a.dosage) if dosage else Q.read_query(a.vcf, a.zarr, a.matrix)
     columns, reports = [], []
     for m in models:
         cv, ca, rep = Q.match_sites(m, query)
-        Q.check_query(m, query, rep, a.min_site_overlap)
+        (Q.check_query_dosage if dosage else Q.check_query)(m, query, rep, a.min_site_overlap)
         columns.append((cv, ca))
         reports.append(rep)
     phased = models[0]["phased"]
@@ -96,11 +104,14 @@ def main(argv=None):
     ids = query["samples"][idx]
     if phased:
         ids = np.array([f"{s}_h{h}" for s in ids for h in (0, 1)], dtype=object)
-    calls, remapped, _ = Q.compact_calls(query, columns)
+    calls, remapped, _ = (Q.compact_dosages if dosage else Q.compact_calls)(query, columns)
     if a.impute_missing:
         # every matched variant once, with the allele and frequency of the first model column that uses it
-        Q.impute_calls(calls, rows, np.concatenate(remapped), np.concatenate([ca for _, ca in columns]),
-                       np.concatenate([m["af"] for m in models]), phased)
+        every = (np.concatenate(remapped), np.concatenate([ca for _, ca in columns]), np.concatenate([m["af"] for m in models]))
+        if dosage:
+            Q.impute_dosages(calls, rows, *every)
+        else:
+            Q.impute_calls(calls, rows, *every, phased)
     for m, (cv, _) in zip(models, columns):
         m["weights_used"] = Q.absent_gamma(m["weights"], cv)
 
@@ -126,8 +137,12 @@ def main(argv=None):
     settings = predict_settings(a)
     written = []
     for m, cv, (_, ca) in zip(models, remapped, columns):
-        X = Q.query_rows(calls_dev, cv, ca, rows, m["K"])
-        z = Q.predict_rows(m, X, settings, dev)
+        if dosage:
+            X = Q.query_rows_dosage(calls_dev, cv, ca, rows, m["K"])
+            z = Q.predict_rows(m, X, settings, dev, unit=G.DOSAGE_UNIT)
+        else:
+            X = Q.query_rows(calls_dev, cv, ca, rows, m["K"])
+            z = Q.predict_rows(m, X, settings, dev)
         del X
         meanlong, sdlong, meanlat, sdlat = m["locs_norm"]
         xy = _to_map_units(z, sdlong, meanlong, sdlat, meanlat)
