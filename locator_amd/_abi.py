@@ -1,7 +1,7 @@
 """The C ABI as include/locator_hip.h declares it, read once at import: the LOC_* constants as module attributes, the
 structs as ctypes Structures (STRUCTS) and the prototypes as (restype, argtypes) pairs (PROTOTYPES).  Nothing else in the
-package restates the header.  include/locator_hip_query.h (later entry points) is read likewise: EXT_PROTOTYPES.  No
-torch here: locator_amd.genotypes and the command line import this module before torch.
+package restates the header.  include/locator_hip_query.h (later entry points) is read likewise: EXT_PROTOTYPES, and so is
+include/locator_hip_regions.h (the regions command): REGION_PROTOTYPES and its LOC_REGION_* constants.  No torch here: locator_amd.genotypes and the command line import this module before torch.
 
 The reader knows the header's spelling, not C: one declaration per `;`, scalar types from _SCALARS, comments only as
 /* */.  Anything else raises with the offending text, so that a header edit cannot silently drop or mis-type an entry."""
@@ -13,6 +13,8 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))
 # entry points added after version 1 of the ABI (the prototype list of locator_hip.h, which tests/test_abi.py pins): the same
 # spelling, read by the same parser into EXT_PROTOTYPES; it declares functions only
 EXT_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_query.h")
+# the regions command's entry points (locator_amd/regions.py): functions and LOC_REGION_* integer constants only
+REGION_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_regions.h")
 
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
             "float": C.c_float, "double": C.c_double}
@@ -101,3 +103,11 @@ with open(EXT_HEADER) as _f:
     _consts, _structs, EXT_PROTOTYPES = parse(_f.read())
 if _consts or _structs or set(EXT_PROTOTYPES) & set(PROTOTYPES):
     raise ValueError(f"{EXT_HEADER} may declare new functions only")
+if not os.path.exists(REGION_HEADER):
+    raise FileNotFoundError(f"{REGION_HEADER} not found: it declares the entry points of the regions command")
+with open(REGION_HEADER) as _f:
+    REGION_CONSTANTS, _structs, REGION_PROTOTYPES = parse(_f.read())
+if (_structs or set(REGION_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES)) or set(REGION_CONSTANTS) & set(CONSTANTS)
+        or not all(k.startswith("LOC_REGION_") and isinstance(v, int) for k, v in REGION_CONSTANTS.items())):
+    raise ValueError(f"{REGION_HEADER} may declare new functions and LOC_REGION_* integer constants only")
+globals().update(REGION_CONSTANTS)

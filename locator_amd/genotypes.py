@@ -508,6 +508,21 @@ def open_group(path, mode="r"):
     return ZarrGroup(path)
 
 
+def walk_outlines(path):
+    """Every [2][n] lon / lat outline of a zarr-v2 map store, as (region, part, lon, lat) float64 in the store's iteration
+    order.  A nested store `Country/Part` gives one region per top-level group and one part per array of it; in a flat
+    store each top-level array is a region of one part, named as the region.  The one walk that plot.read_basemap (to
+    draw) and regions.read_map (to assign) share."""
+    store = ZarrGroup(path)
+    for region in store:
+        node = store[region]
+        members = [(region, node)] if isinstance(node, ZarrArray) else [(m, node[m]) for m in node]
+        for part, arr in members:
+            if isinstance(arr, ZarrArray):
+                xy = np.asarray(arr[:], dtype=np.float64)
+                yield region, part, xy[0], xy[1]
+
+
 def write_zarr_array(path, arr, chunks, compressor=None):
     """Minimal zarr-v2 writer (uncompressed, zlib, "blosc" = Blosc-1 / LZ4 / byte-shuffle as `allel.vcf_to_zarr` writes
     by default, "blosc-zstd" = the same container with zstd streams, "zstd" = numcodecs' plain zstd frames) used to

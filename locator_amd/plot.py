@@ -263,16 +263,8 @@ def error_lines(bp, longlat=False):
 
 def read_basemap(path):
     """[(lon array, lat array), ...]: every [2][n] outline of a zarr-v2 store grouped by country, then part."""
-    from .genotypes import ZarrArray, ZarrGroup
-    store, shapes = ZarrGroup(path), []
-    for country in store:
-        node = store[country]
-        members = [node] if isinstance(node, ZarrArray) else [node[m] for m in node]
-        for arr in members:
-            if isinstance(arr, ZarrArray):
-                xy = np.asarray(arr[:], dtype=np.float64)
-                shapes.append((xy[0], xy[1]))
-    return shapes
+    from .genotypes import walk_outlines
+    return [(lon, lat) for _, _, lon, lat in walk_outlines(path)]
 
 
 # ---------------------------------------------------------------- drawing
