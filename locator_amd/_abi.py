@@ -1,7 +1,8 @@
 """The C ABI as include/locator_hip.h declares it, read once at import: the LOC_* constants as module attributes, the
 structs as ctypes Structures (STRUCTS) and the prototypes as (restype, argtypes) pairs (PROTOTYPES).  Nothing else in the
 package restates the header.  include/locator_hip_query.h (later entry points) is read likewise: EXT_PROTOTYPES, and so is
-include/locator_hip_regions.h (the regions command): REGION_PROTOTYPES and its LOC_REGION_* constants.  No torch here: locator_amd.genotypes and the command line import this module before torch.
+include/locator_hip_regions.h (the regions command): REGION_PROTOTYPES and its LOC_REGION_* constants, and
+include/locator_hip_neighbors.h (the neighbors command): NEIGHBOR_PROTOTYPES and its LOC_IBS_* constants.  No torch here: locator_amd.genotypes and the command line import this module before torch.
 
 The reader knows the header's spelling, not C: one declaration per `;`, scalar types from _SCALARS, comments only as
 /* */.  Anything else raises with the offending text, so that a header edit cannot silently drop or mis-type an entry."""
@@ -15,6 +16,8 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))
 EXT_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_query.h")
 # the regions command's entry points (locator_amd/regions.py): functions and LOC_REGION_* integer constants only
 REGION_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_regions.h")
+# the neighbors command's entry points (locator_amd/neighbors.py): functions and LOC_IBS_* integer constants only
+NEIGHBOR_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_neighbors.h")
 
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
             "float": C.c_float, "double": C.c_double}
@@ -111,3 +114,11 @@ if (_structs or set(REGION_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES))
         or not all(k.startswith("LOC_REGION_") and isinstance(v, int) for k, v in REGION_CONSTANTS.items())):
     raise ValueError(f"{REGION_HEADER} may declare new functions and LOC_REGION_* integer constants only")
 globals().update(REGION_CONSTANTS)
+if not os.path.exists(NEIGHBOR_HEADER):
+    raise FileNotFoundError(f"{NEIGHBOR_HEADER} not found: it declares the entry points of the neighbors command")
+with open(NEIGHBOR_HEADER) as _f:
+    NEIGHBOR_CONSTANTS, _structs, NEIGHBOR_PROTOTYPES = parse(_f.read())
+if (_structs or set(NEIGHBOR_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES) | set(REGION_PROTOTYPES))
+        or not all(k.startswith("LOC_IBS_") and isinstance(v, int) for k, v in NEIGHBOR_CONSTANTS.items())):
+    raise ValueError(f"{NEIGHBOR_HEADER} may declare new functions and LOC_IBS_* integer constants only")
+globals().update(NEIGHBOR_CONSTANTS)
