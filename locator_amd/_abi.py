@@ -2,7 +2,8 @@
 structs as ctypes Structures (STRUCTS) and the prototypes as (restype, argtypes) pairs (PROTOTYPES).  Nothing else in the
 package restates the header.  include/locator_hip_query.h (later entry points) is read likewise: EXT_PROTOTYPES, and so is
 include/locator_hip_regions.h (the regions command): REGION_PROTOTYPES and its LOC_REGION_* constants, and
-include/locator_hip_neighbors.h (the neighbors command): NEIGHBOR_PROTOTYPES and its LOC_IBS_* constants.  No torch here: locator_amd.genotypes and the command line import this module before torch.
+include/locator_hip_neighbors.h (the neighbors command): NEIGHBOR_PROTOTYPES and its LOC_IBS_* constants, and
+include/locator_hip_pca.h (the pca command): PCA_PROTOTYPES and its LOC_PCA_* constants.  No torch here: locator_amd.genotypes and the command line import this module before torch.
 
 The reader knows the header's spelling, not C: one declaration per `;`, scalar types from _SCALARS, comments only as
 /* */.  Anything else raises with the offending text, so that a header edit cannot silently drop or mis-type an entry."""
@@ -18,6 +19,8 @@ EXT_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_query.h")
 REGION_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_regions.h")
 # the neighbors command's entry points (locator_amd/neighbors.py): functions and LOC_IBS_* integer constants only
 NEIGHBOR_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_neighbors.h")
+# the pca command's entry points (locator_amd/pca.py): functions and LOC_PCA_* integer constants only
+PCA_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_pca.h")
 
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
             "float": C.c_float, "double": C.c_double}
@@ -122,3 +125,11 @@ if (_structs or set(NEIGHBOR_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES
         or not all(k.startswith("LOC_IBS_") and isinstance(v, int) for k, v in NEIGHBOR_CONSTANTS.items())):
     raise ValueError(f"{NEIGHBOR_HEADER} may declare new functions and LOC_IBS_* integer constants only")
 globals().update(NEIGHBOR_CONSTANTS)
+if not os.path.exists(PCA_HEADER):
+    raise FileNotFoundError(f"{PCA_HEADER} not found: it declares the entry points of the pca command")
+with open(PCA_HEADER) as _f:
+    PCA_CONSTANTS, _structs, PCA_PROTOTYPES = parse(_f.read())
+if (_structs or set(PCA_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES) | set(REGION_PROTOTYPES) | set(NEIGHBOR_PROTOTYPES))
+        or not all(k.startswith("LOC_PCA_") and isinstance(v, int) for k, v in PCA_CONSTANTS.items())):
+    raise ValueError(f"{PCA_HEADER} may declare new functions and LOC_PCA_* integer constants only")
+globals().update(PCA_CONSTANTS)

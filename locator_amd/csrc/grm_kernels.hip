@@ -1,0 +1,364 @@
+// The genetic relationship matrix of the pca command (locator_amd/pca.py) on the fp32 matrix pipe, and the site loadings of
+// kept eigenvectors.  The definitions are in include/locator_hip_pca.h; the NumPy forms (pca.grm_host, pca.loadings_host) are
+// what tests/test_gpu_pca.py holds both kernels to: element for element where every product and partial sum is an fp32
+// integer, and within the derived fp32 bound otherwise.
+//
+// Arithmetic.  z[s][v] = fl(fl((float)c[s][v] - mean[v]) * scale[v]), 0 for a missing call; G = Z Z'.  Every site carries its
+// own non-integer weight, so unlike the IBS product (ibs_kernels.hip) this one cannot run on the int8 pipe: it runs on
+// v_mfma_f32_32x32x2_f32, whose result is an fp32 fused multiply-add chain in site order.
+//
+// grm_pairs_kernel, work split as in ibs_kernels.hip: grid.x = the tile pairs (I, J), J >= I, of LOC_PCA_TILE = 128 rows a
+// side; grid.y = the site groups, group q owning a contiguous run of LOC_PCA_BLOCK = 32-site blocks.  A workgroup is 4 waves;
+// wave w owns the 64 x 64 quadrant (w >> 1, w & 1) of the 128 x 128 result as 2 x 2 tiles of 32 x 32: 64 accumulator registers.
+// Z is never written to memory.  A thread loads one 16-byte piece of raw counts per side and block, and the 16 means and
+// scales of its sites, and forms the 16 operand values IN REGISTERS on the way to LDS (four operations a value, beside the
+// 64 MFMAs a wave issues per block); a pre-pass would write and re-read 4 N K bytes where this launch reads N K per tile row.
+// Rows past n_rows and sites past K are replaced by 0xff = missing before the values are formed, so pad columns are never
+// interpreted.
+// LDS: [side][row][32 floats], the eight 16-byte pieces of a row XOR-placed by (row >> 1) & 7.  A [row][site] image read one
+// dword per lane would put the 32 rows of an operand on one bank; here a lane reads 16 bytes = four consecutive sites of its
+// row with one ds_read_b128 and feeds four successive MFMAs from them, and the 16 lanes of a ds_read_b128 group (16 rows, one
+// piece each: rows r and r + 1 share a 256-byte bank row, (row >> 1) & 7 takes eight values over the group) cover all 64
+// banks once.
+// Operand lanes: an MFMA takes two sites, lane l supplying row l & 31 at the site of its half l >> 5.  In the step over sites
+// 8 s .. 8 s + 7 of a block, half h reads sites 8 s + 4 h .. + 3 and MFMA q of the step uses element q: the site pair
+// (8 s + q, 8 s + 4 + q), the SAME pair for the A and the B fragment, so every site of the block enters every sum once; the
+// result tile is read by the map that holds for every 32 x 32 shape (rowmap in common.h).
+// Epilogue: the group's fp32 tile goes to its own slab of `work`, all 128 x 128 of it.  grm_reduce_kernel then adds the
+// slabs of an element in group order in double and writes g[i][j] (i <= j) and its copy g[j][i], inside a diagonal tile too:
+// no floating-point atomics, the same bits on every launch, G exactly symmetric.
+//
+// pca_loadings_kernel: t[v][p] = sum_s z[s][v] u[s][p].  Memory-bound (one pass over c), so vector-ALU: a workgroup owns
+// LOC_PCA_SITES = 256 sites, lane l four consecutive ones (one dword of c per row), wave w the components 16 w .. 16 w + 15,
+// 64 accumulators a thread; u is staged through LDS 64 rows at a time, zero-padded to 64 columns, and read as broadcasts.
+#include "common.h"
+
+#include "../../include/locator_hip_pca.h"
+
+#include <algorithm>
+#include <cstdint>
+
+#pragma clang fp contract(off)
+
+constexpr int GR_T = LOC_PCA_TILE;
+constexpr int GR_B = LOC_PCA_BLOCK;
+constexpr int GR_NT = 256;                        // threads: 4 waves
+constexpr int GR_SIDE = GR_T * GR_B;              // floats of one side's image
+static_assert(GR_T == 128 && GR_B == 32 && GR_T * GR_B / 16 == GR_NT, "one 16-site piece per thread and side; 128 x 32");
+
+// the operand value of one count
+__device__ __forceinline__ float gr_z(int cv, float mean, float scale) {
+    const float z = ((float)cv - mean) * scale;   // two roundings: contraction is off
+    return cv < 0 ? 0.f : z;
+}
+__device__ __forceinline__ int gr_byte(uint32_t w, int e) { return (int)(w << (24 - 8 * e)) >> 24; }
+
+// one 16-byte piece of raw counts: row `row` of c, sites k .. k + 15; 0xff (missing) for a row past n_rows or a site past K
+__device__ __forceinline__ uint4 gr_load_piece(const int8_t* __restrict__ c, int64_t row, int n_rows, int64_t k, int64_t K,
+                                               int64_t pitch) {
+    uint4 v = make_uint4(~0u, ~0u, ~0u, ~0u);
+    if (row < n_rows && k < K) {                  // pitch is a multiple of 16 and >= K: a piece that starts below K ends within the row
+        v = *reinterpret_cast<const uint4*>(c + row * pitch + k);
+        const int64_t rem = K - k;
+        if (rem < 16) {
+            uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int r = (int)rem - 4 * e;
+                if (r <= 0) w[e] = ~0u;
+                else if (r < 4) w[e] |= ~0u << (8 * r);
+            }
+            v = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+    }
+    return v;
+}
+
+// 16 floats of a per-site array from site k on, 0 past K (a is 16-byte aligned, k a multiple of 16)
+__device__ __forceinline__ void gr_load_sites(const float* __restrict__ a, int64_t k, int64_t K, f32x4 (&v)[4]) {
+    if (k + 16 <= K) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = *reinterpret_cast<const f32x4*>(a + k + 4 * e);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int x = 0; x < 4; ++x) v[e][x] = k + 4 * e + x < K ? a[k + 4 * e + x] : 0.f;
+    }
+}
+
+__device__ __forceinline__ int gr_at(int row, int piece) { return row * GR_B + ((piece ^ ((row >> 1) & 7)) << 2); }
+
+__device__ __forceinline__ void gr_store_piece(float* side, int row, int chunk, uint4 raw, const f32x4 (&mean)[4],
+                                               const f32x4 (&scale)[4]) {
+    const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        f32x4 z;
+#pragma unroll
+        for (int x = 0; x < 4; ++x) z[x] = gr_z(gr_byte(w[e], x), mean[e][x], scale[e][x]);
+        *reinterpret_cast<f32x4*>(side + gr_at(row, 4 * chunk + e)) = z;
+    }
+}
+
+// tile pair index -> (I, J): row I of the upper triangle holds tiles - I pairs
+__device__ __forceinline__ void gr_pair(int pair, int tiles, int& I, int& J) {
+    I = 0;
+    while (pair >= tiles - I) {
+        pair -= tiles - I;
+        ++I;
+    }
+    J = I + pair;
+}
+
+__global__ __launch_bounds__(GR_NT) void grm_pairs_kernel(const int8_t* __restrict__ c, int n_rows, int64_t K, int64_t pitch,
+                                                          const float* __restrict__ mean, const float* __restrict__ scale,
+                                                          int tiles, int64_t blocks_per_group, float* __restrict__ slabs) {
+    __shared__ __attribute__((aligned(16))) float lds[2 * GR_SIDE];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    int I, J;
+    gr_pair((int)blockIdx.x, tiles, I, J);
+    const bool diag = I == J;
+    const int64_t nblocks = (K + GR_B - 1) / GR_B;
+    const int64_t b0 = (int64_t)blockIdx.y * blocks_per_group;
+    const int64_t b1 = min(nblocks, b0 + blocks_per_group);      // the launcher starts no group past the last block: b0 < b1
+
+    float* const side_i = lds;
+    float* const side_j = diag ? lds : lds + GR_SIDE;
+    const int64_t row_i0 = (int64_t)I * GR_T, row_j0 = (int64_t)J * GR_T;
+    const int srow = t >> 1, schunk = t & 1;      // the piece this thread stages: row srow, sites 16 schunk .. + 15 of the block
+
+    uint4 raw_i, raw_j = make_uint4(~0u, ~0u, ~0u, ~0u);
+    f32x4 mv[4], sv[4];
+    auto request = [&](int64_t b) {
+        const int64_t k = b * GR_B + 16 * schunk;
+        raw_i = gr_load_piece(c, row_i0 + srow, n_rows, k, K, pitch);
+        if (!diag) raw_j = gr_load_piece(c, row_j0 + srow, n_rows, k, K, pitch);
+        gr_load_sites(mean, k, K, mv);
+        gr_load_sites(scale, k, K, sv);
+    };
+
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+
+    const int arow = 64 * (w >> 1) + (lane & 31), brow = 64 * (w & 1) + (lane & 31), half = lane >> 5;
+    request(b0);
+    for (int64_t b = b0; b < b1; ++b) {
+        gr_store_piece(side_i, srow, schunk, raw_i, mv, sv);
+        if (!diag) gr_store_piece(side_j, srow, schunk, raw_j, mv, sv);
+        __syncthreads();
+        if (b + 1 < b1) request(b + 1);
+#pragma unroll
+        for (int s = 0; s < GR_B / 8; ++s) {
+            const int piece = 2 * s + half;
+            f32x4 a[2], bb[2];
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) {
+                a[tt] = *reinterpret_cast<const f32x4*>(side_i + gr_at(arow + 32 * tt, piece));
+                bb[tt] = *reinterpret_cast<const f32x4*>(side_j + gr_at(brow + 32 * tt, piece));
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+                    for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = mfma32(a[tm][q], bb[tn][q], acc[tm][tn]);
+        }
+        __syncthreads();                          // the block is consumed: the next one may overwrite it
+    }
+
+    float* const slab = slabs + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (int64_t)(GR_T * GR_T);
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn) {
+            const int jl = 64 * (w & 1) + 32 * tn + (lane & 31);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int il = 64 * (w >> 1) + 32 * tm + rowmap(r, half);
+                slab[il * GR_T + jl] = acc[tm][tn][r];
+            }
+        }
+}
+
+// grid.x = the tile pairs, grid.y * 256 threads = the 128 x 128 elements of a tile
+__global__ __launch_bounds__(256) void grm_reduce_kernel(const float* __restrict__ slabs, int groups, int n_rows, int tiles,
+                                                         double* __restrict__ g) {
+    int I, J;
+    gr_pair((int)blockIdx.x, tiles, I, J);
+    const int e = (int)blockIdx.y * 256 + (int)threadIdx.x;
+    const int64_t i = (int64_t)I * GR_T + (e >> 7), j = (int64_t)J * GR_T + (e & 127);
+    if (i >= n_rows || j >= n_rows || i > j) return;
+    double s = 0.0;
+    for (int q = 0; q < groups; ++q)
+        s += (double)slabs[((int64_t)q * gridDim.x + blockIdx.x) * (int64_t)(GR_T * GR_T) + e];
+    g[i * n_rows + j] = s;
+    g[j * n_rows + i] = s;
+}
+
+constexpr int PL_NT = 256;
+constexpr int PL_ROWS = 64;                       // rows of u per stage
+constexpr int PL_PW = 16;                         // components per wave
+static_assert(LOC_PCA_SITES == 4 * 64 && LOC_PCA_MAX_NPC == PL_PW * (PL_NT / 64), "4 sites a lane, 16 components a wave");
+
+__global__ __launch_bounds__(PL_NT) void pca_loadings_kernel(const int8_t* __restrict__ c, int n_rows, int64_t K, int64_t pitch,
+                                                             const float* __restrict__ mean, const float* __restrict__ scale,
+                                                             const float* __restrict__ u, int npc, float* __restrict__ t) {
+    __shared__ __attribute__((aligned(16))) float us[PL_ROWS][LOC_PCA_MAX_NPC];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t k = (int64_t)blockIdx.x * LOC_PCA_SITES + 4 * lane;
+    const bool live = k < K;                      // pitch is a multiple of 4 and >= K: a dword that starts below K ends within the row
+    const bool active = PL_PW * w < npc;          // wave-uniform: this wave has components
+    float mv[4], sv[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        mv[e] = k + e < K ? mean[k + e] : 0.f;
+        sv[e] = k + e < K ? scale[k + e] : 0.f;   // a pad byte behind K times 0: never stored either
+    }
+    float acc[4][PL_PW];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int p = 0; p < PL_PW; ++p) acc[e][p] = 0.f;
+
+    for (int i0 = 0; i0 < n_rows; i0 += PL_ROWS) {
+        if (i0) __syncthreads();                  // the previous rows are consumed
+#pragma unroll
+        for (int x = 0; x < PL_ROWS * LOC_PCA_MAX_NPC / PL_NT; ++x) {
+            const int idx = tid + PL_NT * x, r = idx >> 6, p = idx & 63;
+            us[r][p] = (i0 + r < n_rows && p < npc) ? u[(int64_t)(i0 + r) * npc + p] : 0.f;
+        }
+        __syncthreads();
+        if (!active) continue;
+        const int nr = min(PL_ROWS, n_rows - i0);
+#pragma unroll 4
+        for (int r = 0; r < nr; ++r) {
+            const uint32_t wd = live ? *reinterpret_cast<const uint32_t*>(c + (int64_t)(i0 + r) * pitch + k) : ~0u;
+            float z[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) z[e] = gr_z(gr_byte(wd, e), mv[e], sv[e]);
+#pragma unroll
+            for (int p = 0; p < PL_PW; ++p) {
+                const float uu = us[r][PL_PW * w + p];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[e][p] = __builtin_fmaf(z[e], uu, acc[e][p]);
+            }
+        }
+    }
+    if (!active) return;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (k + e < K)
+#pragma unroll
+            for (int p = 0; p < PL_PW; ++p)
+                if (PL_PW * w + p < npc) t[(k + e) * npc + PL_PW * w + p] = acc[e][p];
+}
+
+// (groups launched, blocks per group) for a request of k_groups; 0 groups when there is no site
+static void gr_split(int n_rows, int64_t K, int k_groups, int64_t& groups, int64_t& per) {
+    const int64_t nblocks = (K + GR_B - 1) / GR_B;
+    groups = per = 0;
+    if (nblocks == 0 || n_rows == 0) return;
+    const int64_t tiles = ((int64_t)n_rows + GR_T - 1) / GR_T;
+    const int64_t pairs = tiles * (tiles + 1) / 2;
+    int64_t want = k_groups;
+    if (want == 0) {
+        // few pairs get as many groups as give every compute unit two workgroups; more pairs than that about eight rounds of
+        // shorter workgroups, so that the last, partly filled round is a small share (measured at 528 pairs on 256 units:
+        // 4 groups 15.4 ms, 8 groups 14.4 ms, 12 groups 14.2 ms for half as much scratch again).  A group keeps at least
+        // 16 blocks (512 sites): its 64 KiB slab - written once, read once - stays a small share of its work
+        const int64_t slots = 2 * (int64_t)sr_compute_units();
+        want = pairs <= slots ? slots / pairs : (8 * slots + pairs - 1) / pairs;
+        want = std::max<int64_t>(1, std::min<int64_t>(want, nblocks / 16));
+    }
+    want = std::min<int64_t>(std::min<int64_t>(want, nblocks), 65535);
+    per = (nblocks + want - 1) / want;
+    groups = (nblocks + per - 1) / per;           // groups past the last block are not launched
+}
+
+static bool gr_sizes_ok(const char* who, int n_rows, int64_t K, int k_groups) {
+    if (n_rows < 0 || K < 0 || k_groups < 0 || n_rows >= (1 << 20) || K >= ((int64_t)1 << 31)) {
+        loc_set_error("%s: n_rows=%d K=%lld k_groups=%d (none may be negative; n_rows must stay below 2^20 and K below 2^31)", who,
+                      n_rows, (long long)K, k_groups);
+        return false;
+    }
+    return true;
+}
+
+extern "C" int64_t loc_grm_work_bytes(int n_rows, int64_t K, int k_groups) {
+    if (!gr_sizes_ok("loc_grm_work_bytes", n_rows, K, k_groups)) return -1;
+    int64_t groups, per;
+    gr_split(n_rows, K, k_groups, groups, per);
+    const int64_t tiles = ((int64_t)n_rows + GR_T - 1) / GR_T;
+    return groups * (tiles * (tiles + 1) / 2) * (int64_t)(GR_T * GR_T * sizeof(float));
+}
+
+extern "C" int loc_grm_pairs(const int8_t* c, int n_rows, int64_t K, int64_t pitch, const float* mean, const float* scale,
+                             int k_groups, double* g, void* work, int64_t work_bytes, void* stream) {
+    if (!gr_sizes_ok("loc_grm_pairs", n_rows, K, k_groups)) return -1;
+    if (pitch < K || work_bytes < 0) {
+        loc_set_error("loc_grm_pairs: K=%lld pitch=%lld work_bytes=%lld (pitch >= K, work_bytes >= 0)", (long long)K,
+                      (long long)pitch, (long long)work_bytes);
+        return -1;
+    }
+    if (n_rows == 0) return 0;
+    if (!g || (K > 0 && (!c || !mean || !scale))) {
+        loc_set_error("loc_grm_pairs: null buffer");
+        return -1;
+    }
+    if ((uintptr_t)g % 8 != 0 ||
+        (K > 0 && (pitch % 16 != 0 || (uintptr_t)c % 16 != 0 || (uintptr_t)mean % 16 != 0 || (uintptr_t)scale % 16 != 0))) {
+        loc_set_error("loc_grm_pairs: pitch=%lld, c, mean and scale must be multiples of 16 bytes (rows and site constants are "
+                      "read 16 bytes at a time), g of 8", (long long)pitch);
+        return -1;
+    }
+    int64_t groups, per;
+    gr_split(n_rows, K, k_groups, groups, per);
+    const int64_t tiles = ((int64_t)n_rows + GR_T - 1) / GR_T;
+    const int64_t pairs = tiles * (tiles + 1) / 2;
+    const int64_t need = groups * pairs * (int64_t)(GR_T * GR_T * sizeof(float));
+    if (need > 0 && (!work || work_bytes < need || (uintptr_t)work % 16 != 0)) {
+        loc_set_error("loc_grm_pairs: work of %lld bytes at %p: needs %lld bytes, 16-byte aligned (loc_grm_work_bytes)",
+                      (long long)work_bytes, work, (long long)need);
+        return -1;
+    }
+    if (groups > 0) {
+        hipLaunchKernelGGL(grm_pairs_kernel, dim3((unsigned)pairs, (unsigned)groups), dim3(GR_NT), 0, (hipStream_t)stream, c,
+                           n_rows, K, pitch, mean, scale, (int)tiles, per, (float*)work);
+        LOC_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(grm_reduce_kernel, dim3((unsigned)pairs, GR_T * GR_T / 256), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)work, (int)groups, n_rows, (int)tiles, g);     // no group: every sum is 0
+    LOC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int loc_pca_loadings(const int8_t* c, int n_rows, int64_t K, int64_t pitch, const float* mean, const float* scale,
+                                const float* u, int npc, float* t, void* stream) {
+    if (!gr_sizes_ok("loc_pca_loadings", n_rows, K, 0)) return -1;
+    if (pitch < K || npc < 1 || npc > LOC_PCA_MAX_NPC) {
+        loc_set_error("loc_pca_loadings: K=%lld pitch=%lld npc=%d (pitch >= K, npc 1..%d)", (long long)K, (long long)pitch, npc,
+                      LOC_PCA_MAX_NPC);
+        return -1;
+    }
+    if (K == 0) return 0;
+    if (!t || !mean || !scale || (n_rows > 0 && (!c || !u))) {
+        loc_set_error("loc_pca_loadings: null buffer");
+        return -1;
+    }
+    if (pitch % 16 != 0 || (uintptr_t)c % 16 != 0 || (uintptr_t)mean % 4 != 0 || (uintptr_t)scale % 4 != 0 ||
+        (uintptr_t)u % 4 != 0 || (uintptr_t)t % 4 != 0) {
+        loc_set_error("loc_pca_loadings: pitch=%lld and c must be multiples of 16 bytes, the float arrays of 4", (long long)pitch);
+        return -1;
+    }
+    const int64_t blocks = (K + LOC_PCA_SITES - 1) / LOC_PCA_SITES;
+    hipLaunchKernelGGL(pca_loadings_kernel, dim3((unsigned)blocks), dim3(PL_NT), 0, (hipStream_t)stream, c, n_rows, K, pitch,
+                       mean, scale, u, npc, t);
+    LOC_CHECK_LAUNCH();
+    return 0;
+}
