@@ -21,10 +21,10 @@ extern "C" {
  * and c[j][v] >= 0:  n[i][j] = their number, d[i][j] = sum |c[i][v] - c[j][v]|; d, n [n_rows][n_rows] int32, both symmetric,
  * d[i][i] = 0.  A count of 3 .. 127 is outside the contract (the planes below read its two low bits); 2 * K must stay below 2^31.
  * With the byte planes m = [c >= 0], t1 = [c >= 1], t2 = [c >= 2], a = t1 + t2:  n = M M',  d = A M' + M A' - 2 (T1 T1' + T2 T2'),
- * int8 products accumulated in int32.  The sites are split over k_groups groups of workgroups (0 = chosen by the launcher to
- * fill the device; more groups than blocks of LOC_IBS_BLOCK sites leaves the surplus idle); with more than one group the
- * outputs are zeroed on `stream` and the groups add their integer shares with atomics, so the result is the same for every
- * k_groups.  work / work_bytes: scratch of at least loc_ibs_work_bytes(n_rows, K, k_groups) bytes; this version needs none
+ * int8 products accumulated in int32.  The sites are split over k_groups groups of workgroups, group q owning a contiguous
+ * run of LOC_IBS_BLOCK-site blocks (0 = chosen by the launcher from n_rows, K and the number of compute units; groups past
+ * the last block are not launched); with more than one group launched the outputs are zeroed on `stream` and the groups add
+ * their integer shares with atomics, so the result is the same for every k_groups.  work / work_bytes: scratch of at least loc_ibs_work_bytes(n_rows, K, k_groups) bytes; this version needs none
  * (the function returns 0 and work may be null). */
 int64_t loc_ibs_work_bytes(int n_rows, int64_t K, int k_groups);
 int loc_ibs_pairs(const int8_t* c, int n_rows, int64_t K, int64_t pitch, int k_groups, int32_t* d, int32_t* n, void* work,

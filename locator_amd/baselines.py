@@ -1,0 +1,191 @@
+"""What the baseline commands (neighbors.py: IBS distances and a kNN placement; pca.py: principal components and a PC-regression
+placement) share: the count matrix, the inputs, the common command line, the errors of a placement, the choice of the smallest
+leave-one-out median and the common part of the summaries.  Messages name the command that runs (`prog`: "locator_amd.pca")."""
+import argparse
+import io
+import os
+import zipfile
+
+import numpy as np
+
+
+# ---------------------------------------------------------------- counts
+
+def count_matrix(gt, idx):
+    """(c, P): c int8 [samples][sites] = allele-1 counts of the variants gt[idx] (variants, samples, P), -1 where the call is
+    missing in any allele; P = the ploidy of the calls."""
+    from . import genotypes as G
+    g = np.asarray(gt)[np.asarray(idx, dtype=np.int64)]
+    P = int(g.shape[2])
+    if P not in (1, 2):
+        raise ValueError(f"calls of ploidy {P}: the IBS distance is built for ploidy 1 and 2")
+    c = G.to_allele_counts_1(g).copy()
+    c[G.is_missing(g)] = -1
+    return np.ascontiguousarray(c.T), P
+
+
+def check_counts(c, P):
+    """c as an int8 [N][K] array, after the refusals that precede any device work."""
+    c = np.asarray(c)
+    if c.ndim != 2:
+        raise ValueError(f"count matrix of shape {c.shape}: needs [samples][sites]")
+    if P not in (1, 2):
+        raise ValueError(f"P = {P}: must be 1 or 2")
+    if c.size and int(c.max()) > P:
+        raise ValueError(f"a count of {int(c.max())} exceeds the ploidy {P}: allele-1 counts are 0 .. {P}, missing is -1")
+    if c.shape[1] * P >= 2 ** 31:
+        raise ValueError(f"{c.shape[1]} sites x ploidy {P}: a distance sum could leave int32")
+    c = np.ascontiguousarray(c, dtype=np.int8)
+    return np.where(c < 0, np.int8(-1), c) if c.size and int(c.min()) < -1 else c
+
+
+def padded(c, pitch=None, fill=-1):
+    """c copied into rows of `pitch` bytes (default: the next multiple of 16), the pad filled with `fill`: a value, or a
+    np.random.Generator for arbitrary bytes (the kernel must not interpret them)."""
+    N, K = c.shape
+    pitch = (K + 15) // 16 * 16 if pitch is None else int(pitch)
+    if isinstance(fill, np.random.Generator):
+        buf = fill.integers(-128, 128, (N, max(pitch, 16)), dtype=np.int8)
+    else:
+        buf = np.full((N, max(pitch, 16)), fill, dtype=np.int8)
+    buf[:, :K] = c
+    return buf
+
+
+# ---------------------------------------------------------------- placements
+
+def errors(xy, truth, longlat=False):
+    """Distance of every placement from the true location: Euclidean in map units, or with longlat great-circle km."""
+    if longlat:
+        from .plot import distance_km
+        return distance_km(xy[..., 0], xy[..., 1], truth[..., 0], truth[..., 1])
+    return np.sqrt(((xy - truth) ** 2).sum(axis=-1))
+
+
+def choose_smallest_median(placed, locs, located, longlat, nothing):
+    """(q, per-q median error) of placements [Q][N][2], q = 1 .. Q (--k auto, --p auto): the leave-one-out median error over the
+    located samples for every q and the smallest q that attains the smallest of them; `nothing` refuses when no q has an error."""
+    err = errors(placed[:, located], np.asarray(locs, dtype=np.float64)[located][None], longlat)
+    med = np.array([np.nan if np.isnan(e).all() else np.nanmedian(e) for e in err])
+    if np.isnan(med).all():
+        raise ValueError(nothing)
+    return int(np.nanargmin(med)) + 1, med
+
+
+def r2(a, b):
+    """The squared Pearson correlation, NaN for fewer than two values or a constant."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return float(np.corrcoef(a, b)[0][1] ** 2) if len(a) > 1 else np.nan
+
+
+def num(v):
+    return None if v is None or not np.isfinite(v) else float(v)
+
+
+def placement_summary(c, P, located, xy, locs, longlat, method):
+    """(entries, lines) every baseline reports about its chosen placement xy [N][2]: the summary entries N, n_located, K, P,
+    error_unit, r2_x, r2_y, mean_error, median_error (the command fixes the key order) and the terminal lines of R2 and error."""
+    err = errors(xy[located], locs[located], longlat)
+    ok = ~np.isnan(err)
+    fitted, truth = xy[located][ok], locs[located][ok]
+    r = [r2(fitted[:, a], truth[:, a]) for a in (0, 1)]
+    unit = "km" if longlat else "map units"
+    entries = {"N": int(c.shape[0]), "n_located": int(located.sum()), "K": int(c.shape[1]), "P": int(P), "error_unit": unit,
+               "r2_x": num(r[0]), "r2_y": num(r[1]), "mean_error": num(np.mean(err[ok])) if ok.any() else None,
+               "median_error": num(np.median(err[ok])) if ok.any() else None}
+    lines = [f"R2(x)={r[0]}", f"R2(y)={r[1]}", f"mean {method} leave-one-out error {entries['mean_error']}",
+             f"median {method} leave-one-out error {entries['median_error']} ({unit})"]
+    return entries, lines
+
+
+def save_npz(fh, **arrays):
+    """np.savez_compressed with a fixed member date: two runs that hold the same arrays write the same bytes."""
+    with zipfile.ZipFile(fh, "w", zipfile.ZIP_DEFLATED) as z:
+        for name, arr in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(arr), allow_pickle=False)
+            z.writestr(zipfile.ZipInfo(name + ".npy", (1980, 1, 1, 0, 0, 0)), buf.getvalue(), compress_type=zipfile.ZIP_DEFLATED)
+
+
+# ---------------------------------------------------------------- command
+
+def read_inputs(a, prog):
+    """(gt, samples) by the readers of the fit (genotypes.py), and the refusal of a --matrix with counts above 2 (read_matrix
+    itself lets them contribute nothing)."""
+    from . import genotypes as G
+    if a.zarr is not None:
+        callset = G.open_group(a.zarr, mode="r")
+        return np.asarray(callset["calldata/GT"][:], dtype=np.int8), np.asarray(callset["samples"][:])
+    if a.vcf is not None:
+        vcf = G.read_vcf(a.vcf)
+        return vcf["calldata/GT"], vcf["samples"]
+    import pandas as pd
+    raw = pd.read_csv(a.matrix, sep="\t").drop(labels="sampleID", axis=1).to_numpy()
+    if raw.size and raw.max() > 2:
+        raise SystemExit(f"{prog}: {a.matrix} holds a count of {raw.max()}: allele counts above 2 (ploidy above 2) are not supported")
+    return G.read_matrix(a.matrix)
+
+
+def read_locations(sample_data, samples, prog):
+    """[N][2] x / y of the genotype samples in their order (NaN = not located); every sample must be in the table."""
+    import pandas as pd
+    table = pd.read_csv(sample_data, sep="\t").drop_duplicates("sampleID").set_index("sampleID")
+    ids = np.asarray(samples).astype(str)
+    table.index = table.index.astype(str)
+    missing = [s for s in ids if s not in table.index]
+    if missing:
+        raise SystemExit(f"{prog}: {len(missing)} genotype samples are not in {sample_data} (first: {missing[0]})")
+    return table.reindex(ids)[["x", "y"]].to_numpy(dtype=np.float64)
+
+
+def require_gpu(prog, launch):
+    """The refusal of a device run without a device; `launch` says what the device would have done."""
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit(f"{prog}: no GPU visible ({launch}); pass --host for the NumPy form")
+
+
+def build_parser(prog, description, own):
+    """The command line of a baseline: inputs, site filter and output stem, then what own(parser) adds, then the device."""
+    p = argparse.ArgumentParser(prog=prog, description=description)
+    p.add_argument("--vcf", default=None, help="VCF (optionally gzipped) with the genotypes")
+    p.add_argument("--zarr", default=None, help="zarr-v2 callset with calldata/GT and samples")
+    p.add_argument("--matrix", default=None, help="tab-separated count matrix: sampleID, then 0 / 1 / 2 per site")
+    p.add_argument("--sample_data", required=True, help="tab-separated sampleID, x, y; NaN / NA = to be placed")
+    p.add_argument("--out", required=True, help="output stem")
+    p.add_argument("--min_mac", default=2, type=int, help="minimum allele-1 count of a site, as in a fit (default 2)")
+    p.add_argument("--max_SNPs", default=None, type=int, help="random subset of sites, drawn as a fit with the same --seed draws it")
+    p.add_argument("--seed", default=None, type=int, help="NumPy seed of the --max_SNPs draw")
+    own(p)
+    p.add_argument("--gpu_number", default=None, type=str, help="the GPU to use (sets HIP_VISIBLE_DEVICES)")
+    p.add_argument("--silence", default=False, action="store_true", help="no terminal output")
+    return p
+
+
+def parse_args(parser, argv):
+    """parser.parse_args, and the refusal of a command line without exactly one genotype input."""
+    a = parser.parse_args(argv)
+    if sum(v is not None for v in (a.vcf, a.zarr, a.matrix)) != 1:
+        parser.error("exactly one of --vcf / --zarr / --matrix must be given")
+    return a
+
+
+def prelude(parser, a, launch):
+    """Parsed arguments -> (c, P, samples, locs, idx): the count matrix of the sites a fit would train on, its ploidy, the sample
+    IDs, their locations, the site indices.  Without --host and without a GPU it refuses (require_gpu) before anything is read."""
+    if a.gpu_number is not None:
+        for var in ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
+            os.environ[var] = a.gpu_number
+    if not a.host:
+        require_gpu(parser.prog, launch)
+    from . import genotypes as G
+    if a.seed is not None:
+        np.random.seed(a.seed)
+    gt, samples = read_inputs(a, parser.prog)
+    locs = read_locations(a.sample_data, samples, parser.prog)
+    _, idx = G.filter_snps(gt, min_mac=a.min_mac, max_snps=a.max_SNPs, verbose=False, sites=True)
+    try:
+        c, P = count_matrix(gt, idx)
+    except ValueError as e:
+        raise SystemExit(f"{parser.prog}: {e}") from None
+    return c, P, samples, locs, idx

@@ -7,14 +7,11 @@
 // own non-integer weight, so unlike the IBS product (ibs_kernels.hip) this one cannot run on the int8 pipe: it runs on
 // v_mfma_f32_32x32x2_f32, whose result is an fp32 fused multiply-add chain in site order.
 //
-// grm_pairs_kernel, work split as in ibs_kernels.hip: grid.x = the tile pairs (I, J), J >= I, of LOC_PCA_TILE = 128 rows a
-// side; grid.y = the site groups, group q owning a contiguous run of LOC_PCA_BLOCK = 32-site blocks.  A workgroup is 4 waves;
-// wave w owns the 64 x 64 quadrant (w >> 1, w & 1) of the 128 x 128 result as 2 x 2 tiles of 32 x 32: 64 accumulator registers.
-// Z is never written to memory.  A thread loads one 16-byte piece of raw counts per side and block, and the 16 means and
-// scales of its sites, and forms the 16 operand values IN REGISTERS on the way to LDS (four operations a value, beside the
-// 64 MFMAs a wave issues per block); a pre-pass would write and re-read 4 N K bytes where this launch reads N K per tile row.
-// Rows past n_rows and sites past K are replaced by 0xff = missing before the values are formed, so pad columns are never
-// interpreted.
+// grm_pairs_kernel is the tile-pair skeleton of pair_tiles.h (work split, loading, staging, lanes) with blocks of
+// LOC_PCA_BLOCK = 32 sites and 64 accumulator registers a thread.  Its own:
+// Operands: Z is never written to memory.  A thread loads one 16-byte piece of raw counts per side and block, and the 16
+// means and scales of its sites, and forms the 16 operand values in registers (four operations a value, beside the 64 MFMAs
+// a wave issues per block); a pre-pass would write and re-read 4 N K bytes where this launch reads N K per tile row.
 // LDS: [side][row][32 floats], the eight 16-byte pieces of a row XOR-placed by (row >> 1) & 7.  A [row][site] image read one
 // dword per lane would put the 32 rows of an operand on one bank; here a lane reads 16 bytes = four consecutive sites of its
 // row with one ds_read_b128 and feeds four successive MFMAs from them, and the 16 lanes of a ds_read_b128 group (16 rows, one
@@ -22,8 +19,7 @@
 // banks once.
 // Operand lanes: an MFMA takes two sites, lane l supplying row l & 31 at the site of its half l >> 5.  In the step over sites
 // 8 s .. 8 s + 7 of a block, half h reads sites 8 s + 4 h .. + 3 and MFMA q of the step uses element q: the site pair
-// (8 s + q, 8 s + 4 + q), the SAME pair for the A and the B fragment, so every site of the block enters every sum once; the
-// result tile is read by the map that holds for every 32 x 32 shape (rowmap in common.h).
+// (8 s + q, 8 s + 4 + q), the SAME pair for the A and the B fragment, so every site of the block enters every sum once.
 // Epilogue: the group's fp32 tile goes to its own slab of `work`, all 128 x 128 of it.  grm_reduce_kernel then adds the
 // slabs of an element in group order in double and writes g[i][j] (i <= j) and its copy g[j][i], inside a diagonal tile too:
 // no floating-point atomics, the same bits on every launch, G exactly symmetric.
@@ -32,19 +28,19 @@
 // LOC_PCA_SITES = 256 sites, lane l four consecutive ones (one dword of c per row), wave w the components 16 w .. 16 w + 15,
 // 64 accumulators a thread; u is staged through LDS 64 rows at a time, zero-padded to 64 columns, and read as broadcasts.
 #include "common.h"
+#include "pair_tiles.h"
 
 #include "../../include/locator_hip_pca.h"
 
-#include <algorithm>
 #include <cstdint>
 
 #pragma clang fp contract(off)
 
 constexpr int GR_T = LOC_PCA_TILE;
 constexpr int GR_B = LOC_PCA_BLOCK;
-constexpr int GR_NT = 256;                        // threads: 4 waves
+constexpr int GR_NT = PT_NT;
 constexpr int GR_SIDE = GR_T * GR_B;              // floats of one side's image
-static_assert(GR_T == 128 && GR_B == 32 && GR_T * GR_B / 16 == GR_NT, "one 16-site piece per thread and side; 128 x 32");
+static_assert(GR_T == PT_T && GR_B == 32 && GR_T * GR_B / 16 == GR_NT, "one 16-site piece per thread and side; 128 x 32");
 
 // the operand value of one count
 __device__ __forceinline__ float gr_z(int cv, float mean, float scale) {
@@ -52,27 +48,6 @@ __device__ __forceinline__ float gr_z(int cv, float mean, float scale) {
     return cv < 0 ? 0.f : z;
 }
 __device__ __forceinline__ int gr_byte(uint32_t w, int e) { return (int)(w << (24 - 8 * e)) >> 24; }
-
-// one 16-byte piece of raw counts: row `row` of c, sites k .. k + 15; 0xff (missing) for a row past n_rows or a site past K
-__device__ __forceinline__ uint4 gr_load_piece(const int8_t* __restrict__ c, int64_t row, int n_rows, int64_t k, int64_t K,
-                                               int64_t pitch) {
-    uint4 v = make_uint4(~0u, ~0u, ~0u, ~0u);
-    if (row < n_rows && k < K) {                  // pitch is a multiple of 16 and >= K: a piece that starts below K ends within the row
-        v = *reinterpret_cast<const uint4*>(c + row * pitch + k);
-        const int64_t rem = K - k;
-        if (rem < 16) {
-            uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int r = (int)rem - 4 * e;
-                if (r <= 0) w[e] = ~0u;
-                else if (r < 4) w[e] |= ~0u << (8 * r);
-            }
-            v = make_uint4(w[0], w[1], w[2], w[3]);
-        }
-    }
-    return v;
-}
 
 // 16 floats of a per-site array from site k on, 0 past K (a is 16-byte aligned, k a multiple of 16)
 __device__ __forceinline__ void gr_load_sites(const float* __restrict__ a, int64_t k, int64_t K, f32x4 (&v)[4]) {
@@ -101,23 +76,13 @@ __device__ __forceinline__ void gr_store_piece(float* side, int row, int chunk, 
     }
 }
 
-// tile pair index -> (I, J): row I of the upper triangle holds tiles - I pairs
-__device__ __forceinline__ void gr_pair(int pair, int tiles, int& I, int& J) {
-    I = 0;
-    while (pair >= tiles - I) {
-        pair -= tiles - I;
-        ++I;
-    }
-    J = I + pair;
-}
-
 __global__ __launch_bounds__(GR_NT) void grm_pairs_kernel(const int8_t* __restrict__ c, int n_rows, int64_t K, int64_t pitch,
                                                           const float* __restrict__ mean, const float* __restrict__ scale,
                                                           int tiles, int64_t blocks_per_group, float* __restrict__ slabs) {
     __shared__ __attribute__((aligned(16))) float lds[2 * GR_SIDE];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     int I, J;
-    gr_pair((int)blockIdx.x, tiles, I, J);
+    pt_pair((int)blockIdx.x, tiles, I, J);
     const bool diag = I == J;
     const int64_t nblocks = (K + GR_B - 1) / GR_B;
     const int64_t b0 = (int64_t)blockIdx.y * blocks_per_group;
@@ -132,8 +97,8 @@ __global__ __launch_bounds__(GR_NT) void grm_pairs_kernel(const int8_t* __restri
     f32x4 mv[4], sv[4];
     auto request = [&](int64_t b) {
         const int64_t k = b * GR_B + 16 * schunk;
-        raw_i = gr_load_piece(c, row_i0 + srow, n_rows, k, K, pitch);
-        if (!diag) raw_j = gr_load_piece(c, row_j0 + srow, n_rows, k, K, pitch);
+        raw_i = pt_load_piece(c, row_i0 + srow, n_rows, k, K, pitch);
+        if (!diag) raw_j = pt_load_piece(c, row_j0 + srow, n_rows, k, K, pitch);
         gr_load_sites(mean, k, K, mv);
         gr_load_sites(scale, k, K, sv);
     };
@@ -146,7 +111,7 @@ __global__ __launch_bounds__(GR_NT) void grm_pairs_kernel(const int8_t* __restri
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
 
-    const int arow = 64 * (w >> 1) + (lane & 31), brow = 64 * (w & 1) + (lane & 31), half = lane >> 5;
+    const int arow = pt_arow(w, lane), brow = pt_brow(w, lane), half = pt_half(lane);
     request(b0);
     for (int64_t b = b0; b < b1; ++b) {
         gr_store_piece(side_i, srow, schunk, raw_i, mv, sv);
@@ -190,7 +155,7 @@ __global__ __launch_bounds__(GR_NT) void grm_pairs_kernel(const int8_t* __restri
 __global__ __launch_bounds__(256) void grm_reduce_kernel(const float* __restrict__ slabs, int groups, int n_rows, int tiles,
                                                          double* __restrict__ g) {
     int I, J;
-    gr_pair((int)blockIdx.x, tiles, I, J);
+    pt_pair((int)blockIdx.x, tiles, I, J);
     const int e = (int)blockIdx.y * 256 + (int)threadIdx.x;
     const int64_t i = (int64_t)I * GR_T + (e >> 7), j = (int64_t)J * GR_T + (e & 127);
     if (i >= n_rows || j >= n_rows || i > j) return;
@@ -259,26 +224,12 @@ __global__ __launch_bounds__(PL_NT) void pca_loadings_kernel(const int8_t* __res
                 if (PL_PW * w + p < npc) t[(k + e) * npc + PL_PW * w + p] = acc[e][p];
 }
 
-// (groups launched, blocks per group) for a request of k_groups; 0 groups when there is no site
-static void gr_split(int n_rows, int64_t K, int k_groups, int64_t& groups, int64_t& per) {
-    const int64_t nblocks = (K + GR_B - 1) / GR_B;
-    groups = per = 0;
-    if (nblocks == 0 || n_rows == 0) return;
-    const int64_t tiles = ((int64_t)n_rows + GR_T - 1) / GR_T;
-    const int64_t pairs = tiles * (tiles + 1) / 2;
-    int64_t want = k_groups;
-    if (want == 0) {
-        // few pairs get as many groups as give every compute unit two workgroups; more pairs than that about eight rounds of
-        // shorter workgroups, so that the last, partly filled round is a small share (measured at 528 pairs on 256 units:
-        // 4 groups 15.4 ms, 8 groups 14.4 ms, 12 groups 14.2 ms for half as much scratch again).  A group keeps at least
-        // 16 blocks (512 sites): its 64 KiB slab - written once, read once - stays a small share of its work
-        const int64_t slots = 2 * (int64_t)sr_compute_units();
-        want = pairs <= slots ? slots / pairs : (8 * slots + pairs - 1) / pairs;
-        want = std::max<int64_t>(1, std::min<int64_t>(want, nblocks / 16));
-    }
-    want = std::min<int64_t>(std::min<int64_t>(want, nblocks), 65535);
-    per = (nblocks + want - 1) / want;
-    groups = (nblocks + per - 1) / per;           // groups past the last block are not launched
+// the site groups of a launch (pair_tiles.h); none when there is no site or no row
+static pt_groups gr_split(int n_rows, int64_t K, int k_groups) {
+    // more pairs than workgroup slots: about eight rounds of shorter workgroups (measured at 528 pairs on 256 units: 4 groups
+    // 15.4 ms, 8 groups 14.4 ms, 12 groups 14.2 ms for half as much scratch again).  A group keeps at least 16 blocks (512
+    // sites): its 64 KiB slab - written once, read once - stays a small share of its work
+    return pt_site_groups((K + GR_B - 1) / GR_B, pt_pairs(pt_tiles(n_rows)), k_groups, sr_compute_units(), 8, 16);
 }
 
 static bool gr_sizes_ok(const char* who, int n_rows, int64_t K, int k_groups) {
@@ -292,35 +243,26 @@ static bool gr_sizes_ok(const char* who, int n_rows, int64_t K, int k_groups) {
 
 extern "C" int64_t loc_grm_work_bytes(int n_rows, int64_t K, int k_groups) {
     if (!gr_sizes_ok("loc_grm_work_bytes", n_rows, K, k_groups)) return -1;
-    int64_t groups, per;
-    gr_split(n_rows, K, k_groups, groups, per);
-    const int64_t tiles = ((int64_t)n_rows + GR_T - 1) / GR_T;
-    return groups * (tiles * (tiles + 1) / 2) * (int64_t)(GR_T * GR_T * sizeof(float));
+    return gr_split(n_rows, K, k_groups).groups * pt_pairs(pt_tiles(n_rows)) * (int64_t)(GR_T * GR_T * sizeof(float));
 }
 
 extern "C" int loc_grm_pairs(const int8_t* c, int n_rows, int64_t K, int64_t pitch, const float* mean, const float* scale,
                              int k_groups, double* g, void* work, int64_t work_bytes, void* stream) {
-    if (!gr_sizes_ok("loc_grm_pairs", n_rows, K, k_groups)) return -1;
-    if (pitch < K || work_bytes < 0) {
-        loc_set_error("loc_grm_pairs: K=%lld pitch=%lld work_bytes=%lld (pitch >= K, work_bytes >= 0)", (long long)K,
-                      (long long)pitch, (long long)work_bytes);
+    if (!gr_sizes_ok("loc_grm_pairs", n_rows, K, k_groups) || !pt_sizes_ok("loc_grm_pairs", n_rows, K, pitch, k_groups, work_bytes))
         return -1;
-    }
     if (n_rows == 0) return 0;
     if (!g || (K > 0 && (!c || !mean || !scale))) {
         loc_set_error("loc_grm_pairs: null buffer");
         return -1;
     }
-    if ((uintptr_t)g % 8 != 0 ||
-        (K > 0 && (pitch % 16 != 0 || (uintptr_t)c % 16 != 0 || (uintptr_t)mean % 16 != 0 || (uintptr_t)scale % 16 != 0))) {
-        loc_set_error("loc_grm_pairs: pitch=%lld, c, mean and scale must be multiples of 16 bytes (rows and site constants are "
-                      "read 16 bytes at a time), g of 8", (long long)pitch);
+    if (K > 0 && !pt_rows_aligned("loc_grm_pairs", c, pitch)) return -1;
+    if ((uintptr_t)g % 8 != 0 || (K > 0 && ((uintptr_t)mean % 16 != 0 || (uintptr_t)scale % 16 != 0))) {
+        loc_set_error("loc_grm_pairs: mean and scale must be multiples of 16 bytes (site constants are read 16 bytes at a time), "
+                      "g of 8");
         return -1;
     }
-    int64_t groups, per;
-    gr_split(n_rows, K, k_groups, groups, per);
-    const int64_t tiles = ((int64_t)n_rows + GR_T - 1) / GR_T;
-    const int64_t pairs = tiles * (tiles + 1) / 2;
+    const pt_groups split = gr_split(n_rows, K, k_groups);
+    const int64_t groups = split.groups, tiles = pt_tiles(n_rows), pairs = pt_pairs(tiles);
     const int64_t need = groups * pairs * (int64_t)(GR_T * GR_T * sizeof(float));
     if (need > 0 && (!work || work_bytes < need || (uintptr_t)work % 16 != 0)) {
         loc_set_error("loc_grm_pairs: work of %lld bytes at %p: needs %lld bytes, 16-byte aligned (loc_grm_work_bytes)",
@@ -329,7 +271,7 @@ extern "C" int loc_grm_pairs(const int8_t* c, int n_rows, int64_t K, int64_t pit
     }
     if (groups > 0) {
         hipLaunchKernelGGL(grm_pairs_kernel, dim3((unsigned)pairs, (unsigned)groups), dim3(GR_NT), 0, (hipStream_t)stream, c,
-                           n_rows, K, pitch, mean, scale, (int)tiles, per, (float*)work);
+                           n_rows, K, pitch, mean, scale, (int)tiles, split.per, (float*)work);
         LOC_CHECK_LAUNCH();
     }
     hipLaunchKernelGGL(grm_reduce_kernel, dim3((unsigned)pairs, GR_T * GR_T / 256), dim3(256), 0, (hipStream_t)stream,

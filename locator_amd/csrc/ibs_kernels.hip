@@ -7,31 +7,26 @@
 //     n = M M'          d = A M' + M A' - 2 (T1 T1' + T2 T2')
 // five int8 products per 32-site step and 32 x 32 tile on v_mfma_i32_32x32x32_i8, accumulated in i32: exact.
 //
-// ibs_pairs_kernel, work split: grid.x = the tile pairs (I, J), J >= I, of LOC_IBS_TILE = 128 rows a side; grid.y = the site
-// groups, group g owning a contiguous run of LOC_IBS_BLOCK = 64-site blocks.  A workgroup is 4 waves; wave w owns the 64 x 64
-// quadrant (w >> 1, w & 1) of the 128 x 128 result as 2 x 2 tiles of 32 x 32, for n and for d: 128 accumulator registers.
-// The planes are derived IN REGISTERS on the way from global memory to LDS, not in a pre-pass: a thread loads two 16-byte
-// pieces of raw counts per side and block, and eight bit operations per 4 sites turn them into the four planes (a pre-pass
-// would write and re-read 4 N K bytes of plane images for every launch; here the raw bytes are read once per tile pair and the
-// vector-ALU work, about 150 operations per thread and block, hides under the 40 MFMAs a wave issues per block).  Rows past
-// n_rows and sites past K are replaced by 0xff = missing before the planes are formed, so pad columns are never interpreted.
-// The -2 of the T products is applied to the A-side fragments after the LDS read (bytes 0 / 1 times 0xfe = 0 / -2), so both
-// sides of a tile pair share one LDS image format and a diagonal pair stages its rows once.
+// ibs_pairs_kernel is the tile-pair skeleton of pair_tiles.h (work split, loading, staging, lanes) with blocks of
+// LOC_IBS_BLOCK = 64 sites and, for n and for d, 128 accumulator registers a thread.  Its own:
+// Operands: a thread loads two 16-byte pieces of raw counts per side and block, and eight bit operations per 4 sites turn
+// them into the four planes (a pre-pass would write and re-read 4 N K bytes of plane images for every launch; here the raw
+// bytes are read once per tile pair and the vector-ALU work, about 150 operations per thread and block, hides under the 40
+// MFMAs a wave issues per block).  The -2 of the T products is applied to the A-side fragments after the LDS read (bytes 0 / 1
+// times 0xfe = 0 / -2), so both sides of a tile pair share one LDS image format.
 // LDS: [side][plane][row][64 B], the four 16-byte pieces of a row XOR-placed by (row >> 2) & 3: the 16 lanes of a
-// ds_read_b128 group (rows r .. r + 15, one piece each) then cover all 64 banks once.  The next block's raw pieces are
-// requested before the MFMAs of the current one.
-// Operand lanes: lane l holds 16 consecutive sites of row l & 31, the same 16 for the A and the B fragment of a step, so the
-// sum over sites is complete whatever order the pipe assigns to the 32 sites of a step; the result tile is read by the map
-// that holds for every 32 x 32 shape: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).
+// ds_read_b128 group (rows r .. r + 15, one piece each) then cover all 64 banks once.
+// Operand lanes: lane l holds 16 consecutive sites of row l & 31, the same 16 for the A and the B fragment of a step (half h
+// the sites 32 ks + 16 h .. + 15), so the sum over sites is complete whatever order the pipe assigns to the 32 sites of a step.
 // Epilogue: the tile and, off the diagonal, its mirror; plain stores with one group, integer atomics into zeroed outputs
 // otherwise (any order of integer additions gives the same sums).
 //
 // ibs_knn_kernel: one wave per row; kmax rounds, each the minimum of (D, j) above the previous round's pick.
 #include "common.h"
+#include "pair_tiles.h"
 
 #include "../../include/locator_hip_neighbors.h"
 
-#include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -43,33 +38,12 @@ typedef int32_t ib_i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int IB_T = LOC_IBS_TILE;
 constexpr int IB_B = LOC_IBS_BLOCK;
-constexpr int IB_NT = 256;                        // threads: 4 waves
+constexpr int IB_NT = PT_NT;
 constexpr int IB_PLANE = IB_T * IB_B;             // bytes of one plane of one side
 constexpr int IB_PIECES = IB_T * IB_B / 16 / IB_NT;   // 16-byte pieces per thread, side and block: 2
-static_assert(IB_T == 128 && IB_B == 64 && IB_PIECES == 2, "the wave / quadrant split below is written for 128 x 64");
+static_assert(IB_T == PT_T && IB_B == 64 && IB_PIECES == 2, "the wave / quadrant split below is written for 128 x 64");
 
 enum { IB_M = 0, IB_A = 1, IB_T1 = 2, IB_T2 = 3 };
-
-// one 16-byte piece of raw counts: row `row` of c, sites k .. k + 15; 0xff (missing) for a row past n_rows or a site past K
-__device__ __forceinline__ uint4 ib_load_piece(const int8_t* __restrict__ c, int64_t row, int n_rows, int64_t k, int64_t K,
-                                               int64_t pitch) {
-    uint4 v = make_uint4(~0u, ~0u, ~0u, ~0u);
-    if (row < n_rows && k < K) {                  // pitch is a multiple of 16 and >= K: a piece that starts below K ends within the row
-        v = *reinterpret_cast<const uint4*>(c + row * pitch + k);
-        const int64_t rem = K - k;
-        if (rem < 16) {
-            uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int r = (int)rem - 4 * e;
-                if (r <= 0) w[e] = ~0u;
-                else if (r < 4) w[e] |= ~0u << (8 * r);
-            }
-            v = make_uint4(w[0], w[1], w[2], w[3]);
-        }
-    }
-    return v;
-}
 
 // four raw counts -> the four plane words
 __device__ __forceinline__ void ib_planes(uint32_t w, uint32_t& m, uint32_t& a, uint32_t& t1, uint32_t& t2) {
@@ -107,17 +81,12 @@ __global__ __launch_bounds__(IB_NT) void ibs_pairs_kernel(const int8_t* __restri
                                                           int32_t* __restrict__ n) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[2 * 4 * IB_PLANE];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    int I = 0, rem = blockIdx.x;                  // pair index -> (I, J): row I of the upper triangle holds tiles - I pairs
-    while (rem >= tiles - I) {
-        rem -= tiles - I;
-        ++I;
-    }
-    const int J = I + rem;
+    int I, J;
+    pt_pair((int)blockIdx.x, tiles, I, J);
     const bool diag = I == J;
     const int64_t nblocks = (K + IB_B - 1) / IB_B;
     const int64_t b0 = (int64_t)blockIdx.y * blocks_per_group;
-    const int64_t b1 = min(nblocks, b0 + blocks_per_group);
-    if (b0 >= b1) return;                         // a surplus group (only with ATOMIC: the outputs are zeroed)
+    const int64_t b1 = min(nblocks, b0 + blocks_per_group);      // the launcher starts no group past the last block: b0 < b1
 
     uint8_t* const side_i = lds;
     uint8_t* const side_j = diag ? lds : lds + 4 * IB_PLANE;
@@ -129,8 +98,8 @@ __global__ __launch_bounds__(IB_NT) void ibs_pairs_kernel(const int8_t* __restri
         for (int e = 0; e < IB_PIECES; ++e) {
             const int q = t + IB_NT * e, row = q >> 2, chunk = q & 3;
             const int64_t k = b * IB_B + 16 * chunk;
-            raw_i[e] = ib_load_piece(c, row_i0 + row, n_rows, k, K, pitch);
-            if (!diag) raw_j[e] = ib_load_piece(c, row_j0 + row, n_rows, k, K, pitch);
+            raw_i[e] = pt_load_piece(c, row_i0 + row, n_rows, k, K, pitch);
+            if (!diag) raw_j[e] = pt_load_piece(c, row_j0 + row, n_rows, k, K, pitch);
         }
     };
 
@@ -145,7 +114,7 @@ __global__ __launch_bounds__(IB_NT) void ibs_pairs_kernel(const int8_t* __restri
                 acc_d[tm][tn][r] = 0;
             }
 
-    const int arow = 64 * (w >> 1) + (lane & 31), brow = 64 * (w & 1) + (lane & 31), half = lane >> 5;
+    const int arow = pt_arow(w, lane), brow = pt_brow(w, lane), half = pt_half(lane);
     request(b0);
     for (int64_t b = b0; b < b1; ++b) {
 #pragma unroll
@@ -194,6 +163,7 @@ __global__ __launch_bounds__(IB_NT) void ibs_pairs_kernel(const int8_t* __restri
             const int64_t j = row_j0 + 64 * (w & 1) + 32 * tn + (lane & 31);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
+                // (r & 3) + ... is rowmap(r, half) of common.h, spelled out: see the note on the epilogues in pair_tiles.h
                 const int64_t i = row_i0 + 64 * (w >> 1) + 32 * tm + (r & 3) + 8 * (r >> 2) + 4 * half;
                 if (i < n_rows && j < n_rows) {
                     ib_put<ATOMIC>(n, i * n_rows + j, acc_n[tm][tn][r]);
@@ -262,11 +232,7 @@ extern "C" int64_t loc_ibs_work_bytes(int n_rows, int64_t K, int k_groups) {
 extern "C" int loc_ibs_pairs(const int8_t* c, int n_rows, int64_t K, int64_t pitch, int k_groups, int32_t* d, int32_t* n,
                              void* work, int64_t work_bytes, void* stream) {
     (void)work;
-    if (n_rows < 0 || K < 0 || pitch < K || k_groups < 0 || work_bytes < 0) {
-        loc_set_error("loc_ibs_pairs: n_rows=%d K=%lld pitch=%lld k_groups=%d work_bytes=%lld (none may be negative, pitch >= K)",
-                      n_rows, (long long)K, (long long)pitch, k_groups, (long long)work_bytes);
-        return -1;
-    }
+    if (!pt_sizes_ok("loc_ibs_pairs", n_rows, K, pitch, k_groups, work_bytes)) return -1;
     if (2 * K >= ((int64_t)1 << 31)) {
         loc_set_error("loc_ibs_pairs: K=%lld: a distance sum could leave int32 (2 K must stay below 2^31)", (long long)K);
         return -1;
@@ -276,47 +242,32 @@ extern "C" int loc_ibs_pairs(const int8_t* c, int n_rows, int64_t K, int64_t pit
         loc_set_error("loc_ibs_pairs: null buffer");
         return -1;
     }
-    if (K > 0 && (pitch % 16 != 0 || (uintptr_t)c % 16 != 0)) {
-        loc_set_error("loc_ibs_pairs: pitch=%lld and c must be multiples of 16 bytes (rows are read 16 bytes at a time)",
-                      (long long)pitch);
-        return -1;
-    }
-    const int64_t tiles = ((int64_t)n_rows + IB_T - 1) / IB_T;
-    const int64_t pairs = tiles * (tiles + 1) / 2;
+    if (K > 0 && !pt_rows_aligned("loc_ibs_pairs", c, pitch)) return -1;
+    const int64_t tiles = pt_tiles(n_rows), pairs = pt_pairs(tiles);
     if (pairs > 0x7fffffff) {
         loc_set_error("loc_ibs_pairs: %d rows exceed one launch", n_rows);
         return -1;
     }
+    // more pairs than workgroup slots: about four rounds of shorter workgroups, so that the last, partly filled round is a
+    // small share.  A group keeps at least 8 blocks: its epilogue stays a small share
+    const pt_groups split = pt_site_groups((K + IB_B - 1) / IB_B, pairs, k_groups, sr_compute_units(), 4, 8);
     const size_t out_bytes = (size_t)n_rows * (size_t)n_rows * sizeof(int32_t);
-    const int64_t nblocks = (K + IB_B - 1) / IB_B;
-    int64_t groups = k_groups;
-    if (groups == 0) {
-        // two workgroups fit a compute unit.  Few pairs: as many groups as fill those slots once, and no more (one workgroup
-        // past a full round costs a whole round).  More pairs than slots: about four rounds of shorter workgroups, so that the
-        // last, partly filled round is a small share.  A group keeps at least 8 blocks: its epilogue stays a small share.
-        const int64_t slots = 2 * (int64_t)sr_compute_units();
-        const int64_t want = pairs <= slots ? slots / pairs : (4 * slots + pairs - 1) / pairs;
-        groups = std::max<int64_t>(1, std::min<int64_t>(want, nblocks / 8));
-    }
-    if (groups > 65535) groups = 65535;
-    hipError_t e = hipSuccess;
-    if (K == 0 || groups > 1) {
-        e = hipMemsetAsync(d, 0, out_bytes, (hipStream_t)stream);
+    if (split.groups != 1) {                      // no site: the sums are 0; several groups: they meet in zeroed outputs
+        hipError_t e = hipMemsetAsync(d, 0, out_bytes, (hipStream_t)stream);
         if (e == hipSuccess) e = hipMemsetAsync(n, 0, out_bytes, (hipStream_t)stream);
         if (e != hipSuccess) {
             loc_set_error("loc_ibs_pairs: zeroing the outputs: %s", hipGetErrorString(e));
             return (int)e;
         }
     }
-    if (K == 0) return 0;
-    const int64_t per = (nblocks + groups - 1) / groups;
-    const dim3 grid((unsigned)pairs, (unsigned)groups);
-    if (groups > 1)
-        hipLaunchKernelGGL(ibs_pairs_kernel<true>, grid, dim3(IB_NT), 0, (hipStream_t)stream, c, n_rows, K, pitch, (int)tiles, per,
-                           d, n);
+    if (split.groups == 0) return 0;
+    const dim3 grid((unsigned)pairs, (unsigned)split.groups);
+    if (split.groups > 1)
+        hipLaunchKernelGGL(ibs_pairs_kernel<true>, grid, dim3(IB_NT), 0, (hipStream_t)stream, c, n_rows, K, pitch, (int)tiles,
+                           split.per, d, n);
     else
         hipLaunchKernelGGL(ibs_pairs_kernel<false>, grid, dim3(IB_NT), 0, (hipStream_t)stream, c, n_rows, K, pitch, (int)tiles,
-                           per, d, n);
+                           split.per, d, n);
     LOC_CHECK_LAUNCH();
     return 0;
 }

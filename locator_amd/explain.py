@@ -285,7 +285,7 @@ def main(argv=None):
     if a.seed is not None:
         np.random.seed(a.seed)
     from . import query as Q
-    from .locator import _write_atomic
+    from ._files import write_atomic
 
     # ---- host: read, match, refuse (nothing on the device yet) - as predict
     if a.window_size < 0:
@@ -340,11 +340,11 @@ def main(argv=None):
         counts = np.bincount(col_site, minlength=len(first))
         one = len(models) == 1
         path = a.out + "_snp_importance.txt" if one else f"{a.out}_{m['stem']}_snp_importance.txt"
-        _write_sites(path, m, first, counts, present, stats, _write_atomic)
+        _write_sites(path, m, first, counts, present, stats, write_atomic)
         if a.window_size:
             wpath = a.out + "_window_importance.txt" if one else f"{a.out}_{m['stem']}_window_importance.txt"
             _write_windows(wpath, window_table(m["chrom"][first], m["pos"][first], present, stats, a.window_size),
-                           _write_atomic)
+                           write_atomic)
         print(f"{m['stem']}: {len(rows)} {'haplotype rows' if phased else 'samples'}, {len(first)} sites "
               f"({int(present.sum())} present, {len(first) - int(present.sum())} absent) -> {path}")
         order = np.argsort(-stats[2], kind="stable")[:a.top]

@@ -34,6 +34,7 @@ import time
 import numpy as np
 
 from . import genotypes as G
+from ._files import write_atomic
 
 
 def build_parser():
@@ -167,21 +168,11 @@ def _setup(argv=None):
     if args.gpu_number is not None:
         for var in ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
             os.environ[var] = args.gpu_number
-    _write_atomic(args.out + "_params.json", lambda fh: json.dump(vars(args), fh, indent=2))
+    write_atomic(args.out + "_params.json", lambda fh: json.dump(vars(args), fh, indent=2))
     _PARAMS_TEXT = json.dumps(vars(args), indent=2)
     seed = args.net_seed if args.net_seed is not None else args.seed
     args._net_seed = seed if seed is not None else int.from_bytes(os.urandom(4), "little")
     return args
-
-
-def _write_atomic(path, writer, mode="w"):
-    """Write through a temporary file in the same directory and rename it into place: concurrent replicate workers
-    (and a reader of a half-finished run) never see a truncated file."""
-    import threading
-    tmp = f"{path}.tmp{os.getpid()}_{threading.get_ident()}"     # replicate fits may share a process (one thread each)
-    with open(tmp, mode) as fh:
-        writer(fh)
-    os.replace(tmp, path)
 
 
 def _phased(a=None):
@@ -566,7 +557,7 @@ def save_weights(path, w):
     """--keep_weights artefact: NumPy archive in Keras tensor orientation (the reference keeps a Keras HDF5 file,
     locator.py:332-348; h5py is not available here)."""
     flat = _weight_arrays(w)
-    _write_atomic(path, lambda fh: np.savez(fh, **flat), mode="wb")
+    write_atomic(path, lambda fh: np.savez(fh, **flat), mode="wb")
 
 
 MODEL_FORMAT_VERSION = 1
@@ -593,7 +584,7 @@ def save_model(path, w, meta):
     flat.update(locs_norm=np.asarray(meta["locs_norm"], dtype=np.float64), ploidy=np.int64(meta["ploidy"]),
                 phased=np.bool_(meta["phased"]), format_version=np.int64(MODEL_FORMAT_VERSION),
                 params_json=np.array(str(meta["params_json"])))
-    _write_atomic(path, lambda fh: np.savez(fh, **flat), mode="wb")
+    write_atomic(path, lambda fh: np.savez(fh, **flat), mode="wb")
 
 
 def read_weights(path):
@@ -692,7 +683,7 @@ def write_predlocs(path, xy, sample_ids):
     """`x,y,sampleID` CSV (locator.py:418-433), written atomically."""
     import pandas as pd
     frame = pd.DataFrame({"x": xy[:, 0], "y": xy[:, 1], "sampleID": np.asarray(sample_ids, dtype=object)})
-    _write_atomic(path, lambda fh: frame.to_csv(fh, index=False))
+    write_atomic(path, lambda fh: frame.to_csv(fh, index=False))
 
 
 def predict_locs(model, predgen, sdlong, meanlong, sdlat, meanlat, testlocs, pred, samples, testgen, history,
@@ -718,7 +709,7 @@ def predict_locs(model, predgen, sdlong, meanlong, sdlat, meanlat, testlocs, pre
                   f"median validation error {np.median(dists)}\n")
         if len(history.history.get("loss", [])):
             table = pd.DataFrame(history.history)
-            _write_atomic(_out() + "_history.txt", lambda fh: table.to_csv(fh, sep="\t", index=False))
+            write_atomic(_out() + "_history.txt", lambda fh: table.to_csv(fh, sep="\t", index=False))
     return dists
 
 
@@ -1275,7 +1266,7 @@ def _main_body(pool, t_program):
         if results:
             import pandas as pd
             last = pd.DataFrame(results[-1]["history"])
-            _write_atomic(args.out + "_history.txt", lambda fh: last.to_csv(fh, sep="\t", index=False))
+            write_atomic(args.out + "_history.txt", lambda fh: last.to_csv(fh, sep="\t", index=False))
             plot_history(_H(results[-1]["history"]), results[-1]["dists"])
     elif args.jacknife:
         _jacknife(ac, traingen, testgen, trainlocs, testlocs, predgen, pred, row_ids(samples), sdlong, meanlong, sdlat, meanlat)

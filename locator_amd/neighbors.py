@@ -23,50 +23,24 @@ is no silent fallback: without a GPU the run stops and says so; --host asks for 
 """
 from __future__ import annotations
 
-import argparse
-import io
 import json
-import os
 import sys
-import zipfile
 
 import numpy as np
 
 from . import _abi
+from . import baselines as B
+from ._files import write_atomic
 
 TILE = _abi.LOC_IBS_TILE
 BLOCK = _abi.LOC_IBS_BLOCK
 KMAX_LIMIT = 64
-
-
-# ---------------------------------------------------------------- counts
-
-def count_matrix(gt, idx):
-    """(c, P): c int8 [samples][sites] = allele-1 counts of the variants gt[idx] (variants, samples, P), -1 where the call is
-    missing in any allele; P = the ploidy of the calls."""
-    from . import genotypes as G
-    g = np.asarray(gt)[np.asarray(idx, dtype=np.int64)]
-    P = int(g.shape[2])
-    if P not in (1, 2):
-        raise ValueError(f"calls of ploidy {P}: the IBS distance is built for ploidy 1 and 2")
-    c = G.to_allele_counts_1(g).copy()
-    c[G.is_missing(g)] = -1
-    return np.ascontiguousarray(c.T), P
-
-
-def check_counts(c, P):
-    """c as an int8 [N][K] array, after the refusals that precede any device work."""
-    c = np.asarray(c)
-    if c.ndim != 2:
-        raise ValueError(f"count matrix of shape {c.shape}: needs [samples][sites]")
-    if P not in (1, 2):
-        raise ValueError(f"P = {P}: must be 1 or 2")
-    if c.size and int(c.max()) > P:
-        raise ValueError(f"a count of {int(c.max())} exceeds the ploidy {P}: allele-1 counts are 0 .. {P}, missing is -1")
-    if c.shape[1] * P >= 2 ** 31:
-        raise ValueError(f"{c.shape[1]} sites x ploidy {P}: a distance sum could leave int32")
-    c = np.ascontiguousarray(c, dtype=np.int8)
-    return np.where(c < 0, np.int8(-1), c) if c.size and int(c.min()) < -1 else c
+PROG = "locator_amd.neighbors"
+LAUNCH = "the pair statistics are one loc_ibs_pairs launch"
+NOTHING_TO_CHOOSE_BY = "no located sample has a located neighbour: nothing to choose k by"
+# the key order of {out}_knn_summary.json (with --close: close, n_close_pairs behind them)
+SUMMARY_KEYS = ("N", "n_located", "K", "P", "kmax", "k", "k_auto", "k_chosen_by", "error_unit", "median_error_by_k", "r2_x", "r2_y",
+                "mean_error", "median_error", "pearson_r_ibs_geo", "n_located_pairs", "n_pairs_no_shared_site")
 
 
 # ---------------------------------------------------------------- pair statistics
@@ -74,7 +48,7 @@ def check_counts(c, P):
 def pairs_host(c, chunk=1 << 24):
     """(d, n) int32 [N][N] of a count matrix c [N][K] with values -1, 0 .. 2: the definition.  For every pair, over the sites
     where both counts are >= 0, the number of such sites and the sum of |c_i - c_j|; row i against rows i .. N - 1, mirrored."""
-    c = check_counts(c, 2)
+    c = B.check_counts(c, 2)
     N, K = c.shape
     d, n = np.zeros((N, N), dtype=np.int32), np.zeros((N, N), dtype=np.int32)
     called = c >= 0
@@ -99,23 +73,10 @@ def planes(c):
 def pairs_planes(c):
     """(d, n) by the identity loc_ibs_pairs computes: n = M M', d = A M' + M A' - 2 (T1 T1' + T2 T2').  float64 products of
     small integers are exact below 2^53; the sums are returned as int32."""
-    m, a, t1, t2 = (p.astype(np.float64) for p in planes(check_counts(c, 2)))
+    m, a, t1, t2 = (p.astype(np.float64) for p in planes(B.check_counts(c, 2)))
     am = a @ m.T
     d = am + am.T - 2.0 * (t1 @ t1.T + t2 @ t2.T)
     return d.astype(np.int32), (m @ m.T).astype(np.int32)
-
-
-def padded(c, pitch=None, fill=-1):
-    """c copied into rows of `pitch` bytes (default: the next multiple of 16), the pad filled with `fill`: a value, or a
-    np.random.Generator for arbitrary bytes (the kernel must not interpret them)."""
-    N, K = c.shape
-    pitch = (K + 15) // 16 * 16 if pitch is None else int(pitch)
-    if isinstance(fill, np.random.Generator):
-        buf = fill.integers(-128, 128, (N, max(pitch, 16)), dtype=np.int8)
-    else:
-        buf = np.full((N, max(pitch, 16)), fill, dtype=np.int8)
-    buf[:, :K] = c
-    return buf
 
 
 def pairs_device(c, k_groups=0, pitch=None, pad_fill=-1, device="cuda:0", keep_on_device=False):
@@ -123,9 +84,9 @@ def pairs_device(c, k_groups=0, pitch=None, pad_fill=-1, device="cuda:0", keep_o
     import torch
     from . import _lib
     lib = _lib.load()
-    c = check_counts(c, 2)
+    c = B.check_counts(c, 2)
     N, K = c.shape
-    buf = padded(c, pitch, pad_fill)
+    buf = B.padded(c, pitch, pad_fill)
     with torch.cuda.device(device):
         d_c = torch.from_numpy(buf).to(device)
         d_d = torch.empty((max(N, 1), max(N, 1)), dtype=torch.int32, device=device)
@@ -199,51 +160,11 @@ def placements(nbr, locs):
         return np.transpose(sums / cnt[:, :, None], (1, 0, 2))
 
 
-def errors(xy, truth, longlat=False):
-    """Distance of every placement from the true location: Euclidean in map units, or with longlat great-circle km."""
-    if longlat:
-        from .plot import distance_km
-        return distance_km(xy[..., 0], xy[..., 1], truth[..., 0], truth[..., 1])
-    return np.sqrt(((xy - truth) ** 2).sum(axis=-1))
-
-
-def choose_k(placed, locs, located, longlat=False):
-    """(k, per-k median error): the leave-one-out median error over the located samples for k = 1 .. kmax and the smallest k
-    that attains the smallest of them."""
-    err = errors(placed[:, located], np.asarray(locs, dtype=np.float64)[located][None], longlat)
-    med = np.array([np.nan if np.isnan(e).all() else np.nanmedian(e) for e in err])
-    if np.isnan(med).all():
-        raise ValueError("no located sample has a located neighbour: nothing to choose k by")
-    return int(np.nanargmin(med)) + 1, med
-
-
-# ---------------------------------------------------------------- tables
-
-def _write(path, text, mode="w"):
-    tmp = f"{path}.tmp{os.getpid()}"                 # a temporary file renamed into place: no reader sees half a file
-    with open(tmp, mode) as fh:
-        text(fh) if callable(text) else fh.write(text)
-    os.replace(tmp, path)
-
-
-def _save_npz(fh, **arrays):
-    """np.savez_compressed with a fixed member date: two runs that hold the same arrays write the same bytes."""
-    with zipfile.ZipFile(fh, "w", zipfile.ZIP_DEFLATED) as z:
-        for name, arr in arrays.items():
-            buf = io.BytesIO()
-            np.lib.format.write_array(buf, np.asanyarray(arr), allow_pickle=False)
-            z.writestr(zipfile.ZipInfo(name + ".npy", (1980, 1, 1, 0, 0, 0)), buf.getvalue(), compress_type=zipfile.ZIP_DEFLATED)
-
-
-def _num(v):
-    return None if v is None or not np.isfinite(v) else float(v)
-
-
 def neighbors(c, P, samples, locs, out=None, k="auto", kmax=32, longlat=False, close=None, keep_matrix=False, host=False,
               silence=False, device="cuda:0"):
     """The command's work for a count matrix: returns the summary dict and writes the output files when `out` is given."""
     import pandas as pd
-    c = check_counts(c, P)
+    c = B.check_counts(c, P)
     N, K = c.shape
     samples = np.asarray(samples).astype(str)
     locs = np.asarray(locs, dtype=np.float64).reshape(N, 2)
@@ -258,40 +179,29 @@ def neighbors(c, P, samples, locs, out=None, k="auto", kmax=32, longlat=False, c
         d, n = pairs_host(c)
         nbr, nbr_dist = knn_host(d, n, P, located, kmax)
     else:
-        import torch
-        if not torch.cuda.is_available():
-            raise SystemExit("locator_amd.neighbors: no GPU visible (the pair statistics are one loc_ibs_pairs launch); "
-                             "pass --host for the NumPy form")
+        B.require_gpu(PROG, LAUNCH)
         d_d, d_n = pairs_device(c, device=device, keep_on_device=True)
         nbr, nbr_dist = knn_device(d_d, d_n, N, P, located, kmax, device=device)
         d, n = d_d.cpu().numpy()[:N, :N], d_n.cpu().numpy()[:N, :N]     # downloaded once: the diagnostics are host NumPy
     D = distances(d, n, P)
 
     placed = placements(nbr, locs)
-    k_auto, med = choose_k(placed, locs, located, longlat)
+    k_auto, med = B.choose_smallest_median(placed, locs, located, longlat, NOTHING_TO_CHOOSE_BY)
     k_used = k_auto if k == "auto" else int(k)
     xy = placed[k_used - 1]
-    err = errors(xy[located], locs[located], longlat)
-    ok = ~np.isnan(err)
-    fitted, truth = xy[located][ok], locs[located][ok]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        r2 = [float(np.corrcoef(fitted[:, a], truth[:, a])[0][1] ** 2) if ok.sum() > 1 else np.nan for a in (0, 1)]
+    shared, shared_lines = B.placement_summary(c, P, located, xy, locs, longlat, "kNN")
     li = np.flatnonzero(located)
     iu = np.triu_indices(len(li), 1)
     pa, pb = li[iu[0]], li[iu[1]]
-    geo = errors(locs[pa], locs[pb], longlat)
+    geo = B.errors(locs[pa], locs[pb], longlat)
     gen = D[pa, pb]
     both = ~np.isnan(gen)
     with np.errstate(divide="ignore", invalid="ignore"):
         r_geo = float(np.corrcoef(gen[both], geo[both])[0][1]) if both.sum() > 1 else np.nan
-    unit = "km" if longlat else "map units"
-    summary = {"N": int(N), "n_located": int(located.sum()), "K": int(K), "P": int(P), "kmax": int(kmax),
-               "k": int(k_used), "k_auto": int(k_auto), "k_chosen_by": "auto" if k == "auto" else "--k", "error_unit": unit,
-               "median_error_by_k": [_num(v) for v in med], "r2_x": _num(r2[0]), "r2_y": _num(r2[1]),
-               "mean_error": _num(np.mean(err[ok])) if ok.any() else None,
-               "median_error": _num(np.median(err[ok])) if ok.any() else None,
-               "pearson_r_ibs_geo": _num(r_geo), "n_located_pairs": int(both.sum()),
-               "n_pairs_no_shared_site": int((np.triu(n == 0, 1)).sum())}
+    own = {"kmax": int(kmax), "k": int(k_used), "k_auto": int(k_auto), "k_chosen_by": "auto" if k == "auto" else "--k",
+           "median_error_by_k": [B.num(v) for v in med], "pearson_r_ibs_geo": B.num(r_geo), "n_located_pairs": int(both.sum()),
+           "n_pairs_no_shared_site": int((np.triu(n == 0, 1)).sum())}
+    summary = {key: {**shared, **own}[key] for key in SUMMARY_KEYS}
     pairs = None
     if close is not None:
         ia, ib = np.triu_indices(N, 1)
@@ -305,14 +215,13 @@ def neighbors(c, P, samples, locs, out=None, k="auto", kmax=32, longlat=False, c
 
     lines = [f"{N} samples ({int(located.sum())} located), {K} sites, ploidy {P}",
              f"k = {k_used} ({summary['k_chosen_by']}; leave-one-out median error by k, k = 1 .. {kmax}, smallest at k = {k_auto})",
-             f"R2(x)={r2[0]}", f"R2(y)={r2[1]}", f"mean kNN leave-one-out error {summary['mean_error']}",
-             f"median kNN leave-one-out error {summary['median_error']} ({unit})",
+             *shared_lines,
              f"Pearson r of IBS distance and geographic distance over {int(both.sum())} located pairs = {r_geo}"]
     if pairs is not None:
         lines.append(f"{len(pairs[0])} pairs with IBS distance <= {close}")
     if out is not None:
         frame = pd.DataFrame({"x": xy[:, 0], "y": xy[:, 1], "sampleID": samples.astype(object)})
-        _write(out + "_knn_locs.txt", lambda fh: frame.to_csv(fh, index=False))
+        write_atomic(out + "_knn_locs.txt", lambda fh: frame.to_csv(fh, index=False))
         rows = ["sampleID\trank\tneighborID\tibs_dist\tn_sites\n"]
         for i in range(N):
             for r in range(kmax):
@@ -320,13 +229,13 @@ def neighbors(c, P, samples, locs, out=None, k="auto", kmax=32, longlat=False, c
                 if j < 0:
                     break
                 rows.append(f"{samples[i]}\t{r + 1}\t{samples[j]}\t{float(nbr_dist[i, r])!r}\t{int(n[i, j])}\n")
-        _write(out + "_neighbors.txt", "".join(rows))
-        _write(out + "_knn_summary.json", json.dumps(summary, indent=1) + "\n")
+        write_atomic(out + "_neighbors.txt", "".join(rows))
+        write_atomic(out + "_knn_summary.json", json.dumps(summary, indent=1) + "\n")
         if pairs is not None:
-            _write(out + "_close_pairs.txt", "sampleA\tsampleB\tibs_dist\tn_sites\n" + "".join(
+            write_atomic(out + "_close_pairs.txt", "sampleA\tsampleB\tibs_dist\tn_sites\n" + "".join(
                 f"{samples[a]}\t{samples[b]}\t{float(D[a, b])!r}\t{int(n[a, b])}\n" for a, b in zip(*pairs)))
         if keep_matrix:
-            _write(out + "_ibs.npz", lambda fh: _save_npz(fh, d=d, n=n, samples=samples), mode="wb")
+            write_atomic(out + "_ibs.npz", lambda fh: B.save_npz(fh, d=d, n=n, samples=samples), mode="wb")
     if not silence:
         for line in lines:
             print(line)
@@ -336,47 +245,7 @@ def neighbors(c, P, samples, locs, out=None, k="auto", kmax=32, longlat=False, c
 
 # ---------------------------------------------------------------- command
 
-def read_inputs(a):
-    """(gt, samples) by the readers of the fit (genotypes.py), and the refusal of a --matrix with counts above 2 (read_matrix
-    itself lets them contribute nothing)."""
-    from . import genotypes as G
-    if a.zarr is not None:
-        callset = G.open_group(a.zarr, mode="r")
-        return np.asarray(callset["calldata/GT"][:], dtype=np.int8), np.asarray(callset["samples"][:])
-    if a.vcf is not None:
-        vcf = G.read_vcf(a.vcf)
-        return vcf["calldata/GT"], vcf["samples"]
-    import pandas as pd
-    raw = pd.read_csv(a.matrix, sep="\t").drop(labels="sampleID", axis=1).to_numpy()
-    if raw.size and raw.max() > 2:
-        raise SystemExit(f"locator_amd.neighbors: {a.matrix} holds a count of {raw.max()}: allele counts above 2 (ploidy above "
-                         "2) are not supported")
-    return G.read_matrix(a.matrix)
-
-
-def read_locations(sample_data, samples):
-    """[N][2] x / y of the genotype samples in their order (NaN = not located); every sample must be in the table."""
-    import pandas as pd
-    table = pd.read_csv(sample_data, sep="\t").drop_duplicates("sampleID").set_index("sampleID")
-    ids = np.asarray(samples).astype(str)
-    table.index = table.index.astype(str)
-    missing = [s for s in ids if s not in table.index]
-    if missing:
-        raise SystemExit(f"locator_amd.neighbors: {len(missing)} genotype samples are not in {sample_data} (first: {missing[0]})")
-    return table.reindex(ids)[["x", "y"]].to_numpy(dtype=np.float64)
-
-
-def build_parser():
-    p = argparse.ArgumentParser(prog="locator_amd.neighbors",
-                                description="IBS distances of all sample pairs and a k-nearest-neighbour placement baseline.")
-    p.add_argument("--vcf", default=None, help="VCF (optionally gzipped) with the genotypes")
-    p.add_argument("--zarr", default=None, help="zarr-v2 callset with calldata/GT and samples")
-    p.add_argument("--matrix", default=None, help="tab-separated count matrix: sampleID, then 0 / 1 / 2 per site")
-    p.add_argument("--sample_data", required=True, help="tab-separated sampleID, x, y; NaN / NA = to be placed")
-    p.add_argument("--out", required=True, help="output stem")
-    p.add_argument("--min_mac", default=2, type=int, help="minimum allele-1 count of a site, as in a fit (default 2)")
-    p.add_argument("--max_SNPs", default=None, type=int, help="random subset of sites, drawn as a fit with the same --seed draws it")
-    p.add_argument("--seed", default=None, type=int, help="NumPy seed of the --max_SNPs draw")
+def _own_arguments(p):
     p.add_argument("--k", default="auto", help="neighbours averaged: a number, or `auto` (default): the k in 1 .. --kmax with "
                                                "the smallest leave-one-out median error")
     p.add_argument("--kmax", default=32, type=int, help=f"neighbours listed per sample and largest k tried (default 32, at most {KMAX_LIMIT})")
@@ -386,16 +255,15 @@ def build_parser():
                    help="also list every sample pair with IBS distance <= T in {out}_close_pairs.txt (no default threshold)")
     p.add_argument("--keep_matrix", default=False, action="store_true", help="keep d, n and the sample IDs in {out}_ibs.npz")
     p.add_argument("--host", default=False, action="store_true", help="the NumPy form instead of the GPU (same files)")
-    p.add_argument("--gpu_number", default=None, type=str, help="the GPU to use (sets HIP_VISIBLE_DEVICES)")
-    p.add_argument("--silence", default=False, action="store_true", help="no terminal output")
-    return p
+
+
+def build_parser():
+    return B.build_parser(PROG, "IBS distances of all sample pairs and a k-nearest-neighbour placement baseline.", _own_arguments)
 
 
 def main(argv=None):
     parser = build_parser()
-    a = parser.parse_args(argv)
-    if sum(v is not None for v in (a.vcf, a.zarr, a.matrix)) != 1:
-        parser.error("exactly one of --vcf / --zarr / --matrix must be given")
+    a = B.parse_args(parser, argv)
     if a.k != "auto":
         try:
             a.k = int(a.k)
@@ -407,25 +275,11 @@ def main(argv=None):
         parser.error(f"--k must be `auto` or 1 .. --kmax ({a.kmax})")
     if a.close is not None and not a.close >= 0:
         parser.error("--close must be a distance >= 0")
-    if a.gpu_number is not None:
-        for var in ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
-            os.environ[var] = a.gpu_number
-    if not a.host:
-        import torch
-        if not torch.cuda.is_available():
-            raise SystemExit("locator_amd.neighbors: no GPU visible (the pair statistics are one loc_ibs_pairs launch); "
-                             "pass --host for the NumPy form")
-    from . import genotypes as G
-    if a.seed is not None:
-        np.random.seed(a.seed)
-    gt, samples = read_inputs(a)
-    locs = read_locations(a.sample_data, samples)
-    _, idx = G.filter_snps(gt, min_mac=a.min_mac, max_snps=a.max_SNPs, verbose=False, sites=True)
+    c, P, samples, locs, _ = B.prelude(parser, a, LAUNCH)
     try:
-        c, P = count_matrix(gt, idx)
         neighbors(c, P, samples, locs, a.out, a.k, a.kmax, a.longlat, a.close, a.keep_matrix, a.host, a.silence)
     except ValueError as e:
-        raise SystemExit(f"locator_amd.neighbors: {e}") from None
+        raise SystemExit(f"{PROG}: {e}") from None
     return 0
 
 

@@ -6,7 +6,7 @@ much variance the leading axes hold, which axis carries x and which y, and wheth
 
   python -m locator_amd.pca --vcf genotypes.vcf.gz --sample_data samples.txt --out out/test --npc 10
 
-  counts      c [N][K] int8 exactly as the neighbors command takes them (neighbors.count_matrix over the sites of
+  counts      c [N][K] int8 exactly as the neighbors command takes them (baselines.count_matrix over the sites of
               genotypes.filter_snps with the same --min_mac / --max_SNPs / --seed): -1 = missing, 0 .. P, P = 1 or 2.
   constants   per site over its called entries: p = sum c / (P n_called), mean = P p, scale = 1 / sqrt(P p (1 - p))
               (Patterson's scaling, as smartpca and scikit-allel do), computed in float64 and ROUNDED ONCE TO FLOAT32: the
@@ -24,7 +24,7 @@ much variance the leading axes hold, which axis carries x and which y, and wheth
               p PCs over the located samples by ordinary least squares; located samples are predicted LEAVE-ONE-OUT by the
               hat-matrix identity y_i - r_i / (1 - h_i) (NaN where 1 - h_i < 1e-12), the others from the fit on all located
               samples.  --p auto takes the p with the smallest leave-one-out median error (the smallest such p); errors as
-              neighbors.errors, --longlat included.
+              baselines.errors, --longlat included.
   diagnostics per PC the squared Pearson correlation with x and with y over the located samples.
 
 Outputs: {out}_pca.txt, {out}_pca_eigenvalues.txt, {out}_pca_locs.txt (x,y,sampleID as a predlocs file, but NOT named
@@ -43,19 +43,24 @@ pairwise-complete normalisation instead of mean imputation; an eigen-solver on t
 """
 from __future__ import annotations
 
-import argparse
 import json
-import os
 import sys
 
 import numpy as np
 
 from . import _abi
-from . import neighbors as NB
+from . import baselines as B
+from ._files import write_atomic
 
 TILE = _abi.LOC_PCA_TILE
 BLOCK = _abi.LOC_PCA_BLOCK
 NPC_LIMIT = _abi.LOC_PCA_MAX_NPC
+PROG = "locator_amd.pca"
+LAUNCH = "the relationship matrix is one loc_grm_pairs launch"
+NOTHING_TO_CHOOSE_BY = "no located sample has a leave-one-out prediction: nothing to choose p by"
+# the key order of {out}_pca_summary.json
+SUMMARY_KEYS = ("N", "n_located", "K", "K_used", "P", "npc", "pmax", "p", "p_auto", "p_chosen_by", "error_unit", "median_error_by_p",
+                "r2_x", "r2_y", "mean_error", "median_error", "eigenvalues", "variance_share", "pc_r2_x", "pc_r2_y")
 
 
 # ---------------------------------------------------------------- the definitions
@@ -64,7 +69,7 @@ def site_constants(c, P):
     """(mean float32 [K], scale float32 [K], K_used): per site over its called entries p = sum c / (P n_called), mean = P p,
     scale = 1 / sqrt(P p (1 - p)), float64 rounded once to float32; mean = scale = 0 for a site with no call, p = 0 or p = 1,
     which K_used does not count."""
-    c = NB.check_counts(c, P)
+    c = B.check_counts(c, P)
     called = c >= 0
     n = called.sum(axis=0, dtype=np.int64)
     s = np.where(called, c, 0).sum(axis=0, dtype=np.int64)
@@ -130,7 +135,7 @@ def report_loadings(T, K_used, lam):
 
 def _upload(c, mean, scale, pitch=None, pad_fill=-1, device="cuda:0"):
     import torch
-    buf = NB.padded(c, pitch, pad_fill)
+    buf = B.padded(c, pitch, pad_fill)
     with torch.cuda.device(device):
         return (torch.from_numpy(buf).to(device), torch.from_numpy(np.ascontiguousarray(mean, dtype=np.float32)).to(device),
                 torch.from_numpy(np.ascontiguousarray(scale, dtype=np.float32)).to(device), int(buf.shape[1]))
@@ -227,24 +232,9 @@ def placements_refit(pcs, locs, located, pmax):
     return out
 
 
-def choose_p(placed, locs, located, longlat=False):
-    """(p, per-p median error): the leave-one-out median error over the located samples for p = 1 .. pmax and the smallest p
-    that attains the smallest of them."""
-    err = NB.errors(placed[:, located], np.asarray(locs, dtype=np.float64)[located][None], longlat)
-    med = np.array([np.nan if np.isnan(e).all() else np.nanmedian(e) for e in err])
-    if np.isnan(med).all():
-        raise ValueError("no located sample has a leave-one-out prediction: nothing to choose p by")
-    return int(np.nanargmin(med)) + 1, med
-
-
-def _r2(a, b):
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return float(np.corrcoef(a, b)[0][1] ** 2) if len(a) > 1 else np.nan
-
-
 def pc_r2(pcs, locs, located):
     """[npc][2]: the squared Pearson correlation of every PC with x and with y over the located samples."""
-    return np.array([[_r2(pcs[located, q], locs[located, a]) for a in (0, 1)] for q in range(pcs.shape[1])])
+    return np.array([[B.r2(pcs[located, q], locs[located, a]) for a in (0, 1)] for q in range(pcs.shape[1])])
 
 
 # ---------------------------------------------------------------- the command's work
@@ -253,7 +243,7 @@ def pca(c, P, samples, locs, out=None, npc=10, p="auto", longlat=False, loadings
         silence=False, device="cuda:0", sites=None):
     """The command's work for a count matrix: returns the summary dict and writes the output files when `out` is given."""
     import pandas as pd
-    c = NB.check_counts(c, P)
+    c = B.check_counts(c, P)
     N, K = c.shape
     samples = np.asarray(samples).astype(str)
     locs = np.asarray(locs, dtype=np.float64).reshape(N, 2)
@@ -272,10 +262,7 @@ def pca(c, P, samples, locs, out=None, npc=10, p="auto", longlat=False, loadings
     if host:
         G = grm_host(c, mean, scale)
     else:
-        import torch
-        if not torch.cuda.is_available():
-            raise SystemExit("locator_amd.pca: no GPU visible (the relationship matrix is one loc_grm_pairs launch); "
-                             "pass --host for the NumPy form")
+        B.require_gpu(PROG, LAUNCH)
         on_device = _upload(c, mean, scale, device=device)
         G = grm_device(c, mean, scale, device=device, on_device=on_device)      # downloaded once: the rest is host float64
     lam, U, share = components(G, K_used, npc)
@@ -283,22 +270,15 @@ def pca(c, P, samples, locs, out=None, npc=10, p="auto", longlat=False, loadings
     r2pc = pc_r2(pcs, locs, located)
 
     placed = placements(pcs, locs, located, pmax)
-    p_auto, med = choose_p(placed, locs, located, longlat)
+    p_auto, med = B.choose_smallest_median(placed, locs, located, longlat, NOTHING_TO_CHOOSE_BY)
     p_used = p_auto if p == "auto" else int(p)
     xy = placed[p_used - 1]
-    err = NB.errors(xy[located], locs[located], longlat)
-    ok = ~np.isnan(err)
-    fitted, truth = xy[located][ok], locs[located][ok]
-    r2 = [_r2(fitted[:, a], truth[:, a]) if ok.sum() > 1 else np.nan for a in (0, 1)]
-    unit = "km" if longlat else "map units"
-    num = NB._num
-    summary = {"N": int(N), "n_located": int(located.sum()), "K": int(K), "K_used": int(K_used), "P": int(P), "npc": int(npc),
-               "pmax": int(pmax), "p": int(p_used), "p_auto": int(p_auto), "p_chosen_by": "auto" if p == "auto" else "--p",
-               "error_unit": unit, "median_error_by_p": [num(v) for v in med], "r2_x": num(r2[0]), "r2_y": num(r2[1]),
-               "mean_error": num(np.mean(err[ok])) if ok.any() else None,
-               "median_error": num(np.median(err[ok])) if ok.any() else None,
-               "eigenvalues": [num(v) for v in lam], "variance_share": [num(v) for v in share],
-               "pc_r2_x": [num(v) for v in r2pc[:, 0]], "pc_r2_y": [num(v) for v in r2pc[:, 1]]}
+    shared, shared_lines = B.placement_summary(c, P, located, xy, locs, longlat, "PC-regression")
+    own = {"K_used": int(K_used), "npc": int(npc), "pmax": int(pmax), "p": int(p_used), "p_auto": int(p_auto),
+           "p_chosen_by": "auto" if p == "auto" else "--p", "median_error_by_p": [B.num(v) for v in med],
+           "eigenvalues": [B.num(v) for v in lam], "variance_share": [B.num(v) for v in share],
+           "pc_r2_x": [B.num(v) for v in r2pc[:, 0]], "pc_r2_y": [B.num(v) for v in r2pc[:, 1]]}
+    summary = {key: {**shared, **own}[key] for key in SUMMARY_KEYS}
 
     T = None
     if loadings:
@@ -314,21 +294,20 @@ def pca(c, P, samples, locs, out=None, npc=10, p="auto", longlat=False, loadings
              f"x is carried by PC{best[0] + 1} (R2 {r2pc[best[0], 0]:.3f}), y by PC{best[1] + 1} (R2 {r2pc[best[1], 1]:.3f}) "
              f"among the first {npc} PCs",
              f"p = {p_used} ({summary['p_chosen_by']}; leave-one-out median error by p, p = 1 .. {pmax}, smallest at p = {p_auto})",
-             f"R2(x)={r2[0]}", f"R2(y)={r2[1]}", f"mean PC-regression leave-one-out error {summary['mean_error']}",
-             f"median PC-regression leave-one-out error {summary['median_error']} ({unit})"]
+             *shared_lines]
     if out is not None:
-        NB._write(out + "_pca.txt", "sampleID\t" + "\t".join(f"PC{q + 1}" for q in range(npc)) + "\n" + "".join(
+        write_atomic(out + "_pca.txt", "sampleID\t" + "\t".join(f"PC{q + 1}" for q in range(npc)) + "\n" + "".join(
             f"{samples[i]}\t" + "\t".join(repr(float(v)) for v in pcs[i]) + "\n" for i in range(N)))
-        NB._write(out + "_pca_eigenvalues.txt", "PC\teigenvalue\tvariance_share\tr2_x\tr2_y\n" + "".join(
+        write_atomic(out + "_pca_eigenvalues.txt", "PC\teigenvalue\tvariance_share\tr2_x\tr2_y\n" + "".join(
             f"{q + 1}\t{float(lam[q])!r}\t{float(share[q])!r}\t{float(r2pc[q, 0])!r}\t{float(r2pc[q, 1])!r}\n" for q in range(npc)))
         frame = pd.DataFrame({"x": xy[:, 0], "y": xy[:, 1], "sampleID": samples.astype(object)})
-        NB._write(out + "_pca_locs.txt", lambda fh: frame.to_csv(fh, index=False))
-        NB._write(out + "_pca_summary.json", json.dumps(summary, indent=1) + "\n")
+        write_atomic(out + "_pca_locs.txt", lambda fh: frame.to_csv(fh, index=False))
+        write_atomic(out + "_pca_summary.json", json.dumps(summary, indent=1) + "\n")
         if keep_matrix:
-            NB._write(out + "_grm.npz", lambda fh: NB._save_npz(fh, G=G, K_used=np.int64(K_used), samples=samples), mode="wb")
+            write_atomic(out + "_grm.npz", lambda fh: B.save_npz(fh, G=G, K_used=np.int64(K_used), samples=samples), mode="wb")
         if T is not None:
             idx = np.arange(K, dtype=np.int64) if sites is None else np.asarray(sites, dtype=np.int64)
-            NB._write(out + "_pca_loadings.npz", lambda fh: NB._save_npz(fh, sites=idx, mean=mean, scale=scale, loadings=T),
+            write_atomic(out + "_pca_loadings.npz", lambda fh: B.save_npz(fh, sites=idx, mean=mean, scale=scale, loadings=T),
                       mode="wb")
     if not silence:
         for line in lines:
@@ -339,17 +318,7 @@ def pca(c, P, samples, locs, out=None, npc=10, p="auto", longlat=False, loadings
 
 # ---------------------------------------------------------------- command
 
-def build_parser():
-    p = argparse.ArgumentParser(prog="locator_amd.pca",
-                                description="Principal components of the genotypes and a PC-regression placement baseline.")
-    p.add_argument("--vcf", default=None, help="VCF (optionally gzipped) with the genotypes")
-    p.add_argument("--zarr", default=None, help="zarr-v2 callset with calldata/GT and samples")
-    p.add_argument("--matrix", default=None, help="tab-separated count matrix: sampleID, then 0 / 1 / 2 per site")
-    p.add_argument("--sample_data", required=True, help="tab-separated sampleID, x, y; NaN / NA = to be placed")
-    p.add_argument("--out", required=True, help="output stem")
-    p.add_argument("--min_mac", default=2, type=int, help="minimum allele-1 count of a site, as in a fit (default 2)")
-    p.add_argument("--max_SNPs", default=None, type=int, help="random subset of sites, drawn as a fit with the same --seed draws it")
-    p.add_argument("--seed", default=None, type=int, help="NumPy seed of the --max_SNPs draw")
+def _own_arguments(p):
     p.add_argument("--npc", default=10, type=int, help=f"components kept (default 10, at most {NPC_LIMIT} and samples - 1)")
     p.add_argument("--p", default="auto", help="PCs regressed on: a number, or `auto` (default): the p in 1 .. min(--npc, "
                                                "located samples - 2) with the smallest leave-one-out median error")
@@ -359,16 +328,15 @@ def build_parser():
     p.add_argument("--keep_matrix", default=False, action="store_true", help="keep G, K_used and the sample IDs in {out}_grm.npz")
     p.add_argument("--host", default=False, action="store_true",
                    help="the NumPy form in float64 instead of the GPU (the files differ within the fp32 bounds of the module text)")
-    p.add_argument("--gpu_number", default=None, type=str, help="the GPU to use (sets HIP_VISIBLE_DEVICES)")
-    p.add_argument("--silence", default=False, action="store_true", help="no terminal output")
-    return p
+
+
+def build_parser():
+    return B.build_parser(PROG, "Principal components of the genotypes and a PC-regression placement baseline.", _own_arguments)
 
 
 def main(argv=None):
     parser = build_parser()
-    a = parser.parse_args(argv)
-    if sum(v is not None for v in (a.vcf, a.zarr, a.matrix)) != 1:
-        parser.error("exactly one of --vcf / --zarr / --matrix must be given")
+    a = B.parse_args(parser, argv)
     if a.p != "auto":
         try:
             a.p = int(a.p)
@@ -378,25 +346,11 @@ def main(argv=None):
             parser.error("--p must be `auto` or a whole number >= 1")
     if not 1 <= a.npc <= NPC_LIMIT:
         parser.error(f"--npc must be 1 .. {NPC_LIMIT}")
-    if a.gpu_number is not None:
-        for var in ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
-            os.environ[var] = a.gpu_number
-    if not a.host:
-        import torch
-        if not torch.cuda.is_available():
-            raise SystemExit("locator_amd.pca: no GPU visible (the relationship matrix is one loc_grm_pairs launch); "
-                             "pass --host for the NumPy form")
-    from . import genotypes as G
-    if a.seed is not None:
-        np.random.seed(a.seed)
-    gt, samples = NB.read_inputs(a)
-    locs = NB.read_locations(a.sample_data, samples)
-    _, idx = G.filter_snps(gt, min_mac=a.min_mac, max_snps=a.max_SNPs, verbose=False, sites=True)
+    c, P, samples, locs, idx = B.prelude(parser, a, LAUNCH)
     try:
-        c, P = NB.count_matrix(gt, idx)
         pca(c, P, samples, locs, a.out, a.npc, a.p, a.longlat, a.loadings, a.keep_matrix, a.host, a.silence, sites=idx)
     except ValueError as e:
-        raise SystemExit(f"locator_amd.pca: {e}") from None
+        raise SystemExit(f"{PROG}: {e}") from None
     return 0
 
 

@@ -81,7 +81,8 @@ def main(argv=None):
         np.random.seed(a.seed)
     from . import genotypes as G
     from . import query as Q
-    from .locator import _to_map_units, _write_atomic, predict_settings, write_predlocs
+    from ._files import write_atomic
+    from .locator import _to_map_units, predict_settings, write_predlocs
 
     # ---- host: read, match, refuse (nothing on the device yet)
     models = [Q.load_model(p) for p in Q.model_paths(a.model)]
@@ -119,7 +120,7 @@ def main(argv=None):
         fh.write("model\tsnps\tmatched\tallele_not_1\tabsent\n")
         for r in reports:
             fh.write(f"{r['model']}\t{r['K']}\t{r['matched']}\t{r['allele_not_1']}\t{r['absent']}\n")
-    _write_atomic(a.out + "_sites.txt", sites_report)
+    write_atomic(a.out + "_sites.txt", sites_report)
     for r in reports:
         print(f"{r['model']}: {r['matched']} of {r['K']} sites matched ({r['allele_not_1']} with allele != 1), "
               f"{r['absent']} absent")
@@ -150,7 +151,7 @@ def main(argv=None):
         write_predlocs(path, xy, ids)
         written.append(path)
     if len(models) > 1:
-        _centroids(written, a.out, _write_atomic)
+        _centroids(written, a.out, write_atomic)
     print(f"predicted {len(ids)} rows with {len(models)} model(s) in {time.time() - t0:.2f} s")
     return 0
 

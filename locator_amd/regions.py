@@ -32,6 +32,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _abi
+from ._files import write_atomic
 
 TILE = _abi.LOC_REGION_TILE
 STAGE = _abi.LOC_REGION_STAGE
@@ -309,10 +310,7 @@ def _fmt(v):
 
 
 def _write_table(path, header, rows):
-    tmp = f"{path}.tmp{os.getpid()}"                 # a temporary file renamed into place: no reader sees half a table
-    with open(tmp, "w") as fh:
-        fh.write("".join("\t".join(_fmt(v) for v in row) + "\n" for row in [header] + rows))
-    os.replace(tmp, path)
+    write_atomic(path, "".join("\t".join(_fmt(v) for v in row) + "\n" for row in [header] + rows))
 
 
 def regions(indir, rs, out=None, sample_data=None, longlat=False, snap=0.0, bandwidth=0.2, host=False, silence=False):

@@ -43,7 +43,7 @@ def test_site_counts_around_the_block(K):
 @pytest.mark.parametrize("K", [3 * B + 1, 5 * B + 7, 7 * B])
 @pytest.mark.parametrize("k_groups", [1, 2, 3, 0])
 def test_site_groups(K, k_groups):
-    """3 B + 1: 4 blocks in groups of 4 / 2, 2 / 2, 2, 0 (the third group idle); 5 B + 7: 6 blocks, the last partial, in
+    """3 B + 1: 4 blocks in groups of 4 / 2, 2 / 2, 2 (the third group not launched); 5 B + 7: 6 blocks, the last partial, in
     groups of 6 / 3, 3 / 2, 2, 2; 7 B: 7 blocks as 7 / 4, 3 / 3, 3, 1."""
     both(U.counts(T + 1, K, 30 + K), k_groups=k_groups)
 

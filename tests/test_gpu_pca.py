@@ -13,7 +13,7 @@ import os
 import numpy as np
 import pytest
 
-from locator_amd import neighbors as NB
+from locator_amd import baselines as BL
 from locator_amd import pca as P
 from tests import pca_util as U
 
@@ -272,10 +272,11 @@ def test_the_command_against_host_on_planted_clines(tmp_path):
     want = P.report_loadings(P.loadings_host(c, mean, scale, V.astype(np.float32)), K_used, lam)
     lim = U.loadings_bound(c, mean, scale, V.astype(np.float32)) / np.sqrt(K_used * lam)[None]
     assert (np.abs(ld["loadings"] - want) <= lim * (1 + 1e-12)).all()
-    # --p auto: what choose_p returns on the host from the device's own G
+    # --p auto: what choose_smallest_median returns on the host from the device's own G
     pcs = P.scores(lam, V)
     assert np.array_equal(pcs, pd_)
-    assert sdev["p"] == sdev["p_auto"] == P.choose_p(P.placements(pcs, locs, located, sdev["pmax"]), locs, located)[0]
+    placed = P.placements(pcs, locs, located, sdev["pmax"])
+    assert sdev["p"] == sdev["p_auto"] == BL.choose_smallest_median(placed, locs, located, False, P.NOTHING_TO_CHOOSE_BY)[0]
     assert sdev["pmax"] == npc
     # a fixed --p 2: the placements are the refit from the device scores
     two = run(tmp_path, "two", vcf, sd, "--npc", str(npc), "--p", "2")
@@ -306,8 +307,8 @@ def test_the_command_on_the_golden_vcf(tmp_path):
     vcf = G.read_vcf(U.VCF)
     gt, samples = vcf["calldata/GT"], vcf["samples"]
     _, idx = G.filter_snps(gt, min_mac=2, max_snps=None, verbose=False, sites=True)
-    c, ploidy = NB.count_matrix(gt, idx)
-    locs = NB.read_locations(U.SAMPLE_DATA, samples)
+    c, ploidy = BL.count_matrix(gt, idx)
+    locs = BL.read_locations(U.SAMPLE_DATA, samples, P.PROG)
     again = str(tmp_path / "again")
     P.pca(c, ploidy, samples, locs, again, npc=8, loadings=True, keep_matrix=True, silence=True, sites=idx)
     for name in names:

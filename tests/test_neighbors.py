@@ -10,6 +10,7 @@ import re
 import numpy as np
 import pytest
 
+from locator_amd import baselines as BL
 from locator_amd import neighbors as NB
 from tests import neighbors_util as U
 
@@ -50,7 +51,7 @@ def test_haploid_counts():
     assert d.tolist() == [[0, 2, 2], [2, 0, 2], [2, 2, 0]] and n.tolist() == [[4, 3, 4], [3, 4, 4], [4, 4, 5]]
     assert NB.distances(d, n, 1)[0, 1] == 2 / 3 and NB.distances(d, n, 2)[0, 1] == 2 / 6   # one division by P n
     with pytest.raises(ValueError, match="exceeds the ploidy 1"):
-        NB.check_counts(np.array([[0, 2]], dtype=np.int8), 1)
+        BL.check_counts(np.array([[0, 2]], dtype=np.int8), 1)
 
 
 @pytest.mark.parametrize("P", [1, 2])
@@ -75,10 +76,10 @@ def test_count_matrix_missing_stays_missing():
     gt = np.array([[[0, 1], [1, 1], [-1, 1], [0, -1], [-1, -1]],
                    [[0, 0], [1, 0], [1, 1], [0, 0], [1, 0]],
                    [[1, 1], [1, 1], [1, 1], [1, 1], [1, 1]]], dtype=np.int8)
-    c, P = NB.count_matrix(gt, [0, 1])
+    c, P = BL.count_matrix(gt, [0, 1])
     assert P == 2 and c.dtype == np.int8 and c.shape == (5, 2)
     assert c.T.tolist() == [[1, 2, -1, -1, -1], [0, 1, 2, 0, 1]]              # a partly missing call counts as missing
-    c1, P1 = NB.count_matrix(gt.reshape(3, 10, 1), [1])
+    c1, P1 = BL.count_matrix(gt.reshape(3, 10, 1), [1])
     assert P1 == 1 and c1[:, 0].tolist() == [0, 0, 1, 0, 1, 1, 0, 0, 1, 0]
 
 
@@ -146,8 +147,8 @@ def test_k_auto_is_the_argmin_of_the_recorded_errors(tmp_path):
 def test_longlat_errors_are_the_haversine_of_plot():
     from locator_amd.plot import distance_km
     xy, truth = np.array([[10.0, 50.0], [0.0, 0.0]]), np.array([[11.0, 51.0], [0.0, 1.0]])
-    assert np.array_equal(NB.errors(xy, truth, True), distance_km(xy[:, 0], xy[:, 1], truth[:, 0], truth[:, 1]))
-    assert NB.errors(xy, truth)[1] == 1.0
+    assert np.array_equal(BL.errors(xy, truth, True), distance_km(xy[:, 0], xy[:, 1], truth[:, 0], truth[:, 1]))
+    assert BL.errors(xy, truth)[1] == 1.0
 
 
 # ------------------------------------------------------------------ the binding
@@ -207,7 +208,7 @@ def test_the_command_on_the_golden_vcf(golden_run):
     assert np.array_equal(z["d"], z["d"].T) and not np.diag(z["d"]).any()
     assert not [f for f in os.listdir(os.path.dirname(out)) if "predlocs" in f or ".tmp" in f]
     # the tie rule is not cosmetic here: most located rows have an exact tie inside their first 33 neighbours
-    located = ~np.isnan(NB.read_locations(U.SAMPLE_DATA, z["samples"])).any(axis=1)
+    located = ~np.isnan(BL.read_locations(U.SAMPLE_DATA, z["samples"], NB.PROG)).any(axis=1)
     nbr, dd = NB.knn_host(z["d"], z["n"], 2, located, 33)
     assert int(((np.diff(dd, axis=1) == 0).any(axis=1) & located).sum()) == 391
     # ... and the table holds exactly these rows
@@ -224,7 +225,7 @@ def test_max_snps_draws_the_sites_a_fit_would(tmp_path):
     gt = G.read_vcf(vcf)["calldata/GT"]
     np.random.seed(7)
     _, idx = G.filter_snps(gt, min_mac=2, max_snps=50, verbose=False, sites=True)
-    c, P = NB.count_matrix(gt, idx)
+    c, P = BL.count_matrix(gt, idx)
     z = np.load(out + "_ibs.npz")
     assert json.load(open(out + "_knn_summary.json"))["K"] == 50
     assert np.array_equal(z["d"], NB.pairs_host(c)[0])
@@ -282,4 +283,4 @@ def test_refusals(tmp_path, capsys):
     with pytest.raises(ValueError, match="exceeds the ploidy 2"):
         NB.pairs_host(np.array([[0, 3]], dtype=np.int8))
     with pytest.raises(ValueError, match="could leave int32"):
-        NB.check_counts(np.lib.stride_tricks.as_strided(np.zeros(1, dtype=np.int8), (1, 2 ** 30), (0, 0)), 2)
+        BL.check_counts(np.lib.stride_tricks.as_strided(np.zeros(1, dtype=np.int8), (1, 2 ** 30), (0, 0)), 2)

@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+from locator_amd import baselines as BL
 from locator_amd import pca as P
 from tests import pca_util as U
 
@@ -96,10 +97,10 @@ def test_choose_p_ties_go_to_the_smaller_p():
     located = np.array([True, True, True, False])
     placed = np.zeros((3, 4, 2))
     placed[0] += 5.0                                                                     # p = 1 far off, p = 2 and 3 equal
-    p, med = P.choose_p(placed, locs, located)
+    p, med = BL.choose_smallest_median(placed, locs, located, False, P.NOTHING_TO_CHOOSE_BY)
     assert p == 2 and med[1] == med[2] == 1.0 and med[0] > med[1]
     with pytest.raises(ValueError, match="nothing to choose p by"):
-        P.choose_p(np.full((2, 4, 2), np.nan), locs, located)
+        BL.choose_smallest_median(np.full((2, 4, 2), np.nan), locs, located, False, P.NOTHING_TO_CHOOSE_BY)
 
 
 def test_pc_r2_names_the_axis():
@@ -213,6 +214,27 @@ def test_without_a_gpu_the_command_stops_unless_host(tmp_path, monkeypatch):
     with pytest.raises(SystemExit, match="no GPU visible.*loc_grm_pairs.*--host"):
         P.pca(np.zeros((4, 3), dtype=np.int8), 2, list("abcd"), np.arange(8.0).reshape(4, 2), str(tmp_path / "o"), npc=2)
     assert not os.listdir(tmp_path)
+
+
+def test_refusals_from_shared_code_name_this_command(tmp_path):
+    ids = [f"msp_{i}" for i in range(48, 54)]
+    g = np.random.default_rng(3).integers(0, 3, (6, 30))
+
+    def matrix(path, g, ids):
+        with open(path, "w") as fh:
+            fh.write("sampleID\t" + "\t".join(f"v{k}" for k in range(g.shape[1])) + "\n")
+            for s, row in zip(ids, g):
+                fh.write(s + "\t" + "\t".join(str(v) for v in row) + "\n")
+        return str(path)
+
+    base = ["--sample_data", U.SAMPLE_DATA, "--out", str(tmp_path / "o"), "--host", "--silence", "--npc", "2"]
+    g3 = g.copy()
+    g3[2, 5] = 3
+    with pytest.raises(SystemExit, match="^locator_amd.pca: .*count of 3.*above 2"):
+        P.main(["--matrix", matrix(tmp_path / "three.txt", g3, ids)] + base)
+    with pytest.raises(SystemExit, match="^locator_amd.pca: 1 genotype samples are not in .*first: nobody"):
+        P.main(["--matrix", matrix(tmp_path / "who.txt", g, ids[:5] + ["nobody"])] + base)
+    assert P.main(["--matrix", matrix(tmp_path / "ok.txt", g, ids)] + base) == 0
 
 
 def test_refusals(tmp_path, capsys):

@@ -18,6 +18,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from locator_amd import _lib  # noqa: E402
+from locator_amd import baselines as BL  # noqa: E402
 from locator_amd import neighbors as NB  # noqa: E402
 
 I8_SUSTAINED_TOPS = 3557.0
@@ -39,7 +40,7 @@ def one(N, K, missing, launches, sub, k_groups, rng):
     c = rng.binomial(2, np.broadcast_to(freq, (N, K))).astype(np.int8)
     c[rng.random((N, K)) < missing] = -1
     lib = _lib.load()
-    buf = NB.padded(c)
+    buf = BL.padded(c)
     d_c = torch.from_numpy(buf).cuda()
     d_d = torch.empty((N, N), dtype=torch.int32, device="cuda")
     d_n = torch.empty_like(d_d)

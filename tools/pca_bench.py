@@ -20,7 +20,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from locator_amd import _lib  # noqa: E402
-from locator_amd import neighbors as NB  # noqa: E402
+from locator_amd import baselines as BL  # noqa: E402
 from locator_amd import pca as P  # noqa: E402
 
 FP32_MATRIX_PEAK_TF = 157.3
@@ -42,7 +42,7 @@ def one(N, K, missing, launches, sub, k_groups, rng):
     c[rng.random((N, K)) < missing] = -1
     mean, scale, K_used = P.site_constants(c, 2)
     lib = _lib.load()
-    buf = NB.padded(c)
+    buf = BL.padded(c)
     d_c = torch.from_numpy(buf).cuda()
     d_mean, d_scale = torch.from_numpy(mean).cuda(), torch.from_numpy(scale).cuda()
     d_g = torch.empty((N, N), dtype=torch.float64, device="cuda")
