@@ -3,7 +3,8 @@ structs as ctypes Structures (STRUCTS) and the prototypes as (restype, argtypes)
 package restates the header.  include/locator_hip_query.h (later entry points) is read likewise: EXT_PROTOTYPES, and so is
 include/locator_hip_regions.h (the regions command): REGION_PROTOTYPES and its LOC_REGION_* constants, and
 include/locator_hip_neighbors.h (the neighbors command): NEIGHBOR_PROTOTYPES and its LOC_IBS_* constants, and
-include/locator_hip_pca.h (the pca command): PCA_PROTOTYPES and its LOC_PCA_* constants.  No torch here: locator_amd.genotypes and the command line import this module before torch.
+include/locator_hip_pca.h (the pca command): PCA_PROTOTYPES and its LOC_PCA_* constants, and
+include/locator_hip_ld.h (the ld command): LD_PROTOTYPES and its LOC_LD_* constants.  No torch here: locator_amd.genotypes and the command line import this module before torch.
 
 The reader knows the header's spelling, not C: one declaration per `;`, scalar types from _SCALARS, comments only as
 /* */.  Anything else raises with the offending text, so that a header edit cannot silently drop or mis-type an entry."""
@@ -21,6 +22,8 @@ REGION_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_regions.h")
 NEIGHBOR_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_neighbors.h")
 # the pca command's entry points (locator_amd/pca.py): functions and LOC_PCA_* integer constants only
 PCA_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_pca.h")
+# the ld command's entry point (locator_amd/ld.py): functions and LOC_LD_* integer constants only
+LD_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_ld.h")
 
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
             "float": C.c_float, "double": C.c_double}
@@ -133,3 +136,12 @@ if (_structs or set(PCA_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES) | s
         or not all(k.startswith("LOC_PCA_") and isinstance(v, int) for k, v in PCA_CONSTANTS.items())):
     raise ValueError(f"{PCA_HEADER} may declare new functions and LOC_PCA_* integer constants only")
 globals().update(PCA_CONSTANTS)
+if not os.path.exists(LD_HEADER):
+    raise FileNotFoundError(f"{LD_HEADER} not found: it declares the entry point of the ld command")
+with open(LD_HEADER) as _f:
+    LD_CONSTANTS, _structs, LD_PROTOTYPES = parse(_f.read())
+if (_structs or set(LD_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES) | set(REGION_PROTOTYPES) | set(NEIGHBOR_PROTOTYPES)
+                                      | set(PCA_PROTOTYPES))
+        or not all(k.startswith("LOC_LD_") and isinstance(v, int) for k, v in LD_CONSTANTS.items())):
+    raise ValueError(f"{LD_HEADER} may declare new functions and LOC_LD_* integer constants only")
+globals().update(LD_CONSTANTS)

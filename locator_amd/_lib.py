@@ -30,7 +30,8 @@ def use_library(path):
 # The structs and every entry point's (restype, argtypes) come from include/locator_hip.h (locator_amd/_abi.py): a new entry
 # point needs its prototype there (since version 1 of the ABI: in include/locator_hip_query.h, EXT_SIGNATURES; the regions
 # command's: include/locator_hip_regions.h, REGION_SIGNATURES; the neighbors command's: include/locator_hip_neighbors.h,
-# NEIGHBOR_SIGNATURES; the pca command's: include/locator_hip_pca.h, PCA_SIGNATURES) and nothing here.
+# NEIGHBOR_SIGNATURES; the pca command's: include/locator_hip_pca.h, PCA_SIGNATURES; the ld command's:
+# include/locator_hip_ld.h, LD_SIGNATURES) and nothing here.
 Dims, Layout, Tuning, Net, CbState = (_abi.STRUCTS[n] for n in ("loc_dims", "loc_layout", "loc_tuning", "loc_net",
                                                                 "loc_cb_state"))
 SIGNATURES = _abi.PROTOTYPES
@@ -38,6 +39,7 @@ EXT_SIGNATURES = _abi.EXT_PROTOTYPES
 REGION_SIGNATURES = _abi.REGION_PROTOTYPES
 NEIGHBOR_SIGNATURES = _abi.NEIGHBOR_PROTOTYPES
 PCA_SIGNATURES = _abi.PCA_PROTOTYPES
+LD_SIGNATURES = _abi.LD_PROTOTYPES
 
 
 class LocatorHipError(RuntimeError):
@@ -58,7 +60,7 @@ def load():
             "or `make -C locator_amd/csrc`.  locator_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **REGION_SIGNATURES, **NEIGHBOR_SIGNATURES,
-                              **PCA_SIGNATURES}.items():
+                              **PCA_SIGNATURES, **LD_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

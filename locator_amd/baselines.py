@@ -11,9 +11,7 @@ import numpy as np
 
 # ---------------------------------------------------------------- counts
 
-def count_matrix(gt, idx):
-    """(c, P): c int8 [samples][sites] = allele-1 counts of the variants gt[idx] (variants, samples, P), -1 where the call is
-    missing in any allele; P = the ploidy of the calls."""
+def _counts_by_site(gt, idx):
     from . import genotypes as G
     g = np.asarray(gt)[np.asarray(idx, dtype=np.int64)]
     P = int(g.shape[2])
@@ -21,7 +19,20 @@ def count_matrix(gt, idx):
         raise ValueError(f"calls of ploidy {P}: the IBS distance is built for ploidy 1 and 2")
     c = G.to_allele_counts_1(g).copy()
     c[G.is_missing(g)] = -1
+    return c, P
+
+
+def count_matrix(gt, idx):
+    """(c, P): c int8 [samples][sites] = allele-1 counts of the variants gt[idx] (variants, samples, P), -1 where the call is
+    missing in any allele; P = the ploidy of the calls."""
+    c, P = _counts_by_site(gt, idx)
     return np.ascontiguousarray(c.T), P
+
+
+def count_matrix_sites(gt, idx):
+    """(ct, P): count_matrix's values site-major, int8 [sites][samples], not transposed: what the ld command compares."""
+    c, P = _counts_by_site(gt, idx)
+    return np.ascontiguousarray(c, dtype=np.int8), P
 
 
 def check_counts(c, P):
@@ -126,6 +137,25 @@ def read_inputs(a, prog):
     return G.read_matrix(a.matrix)
 
 
+def read_inputs_sites(a, prog):
+    """(gt, samples, chrom, pos) for the LD window: read_inputs' answers and the variants' CHROM / POS tables.  A --matrix has
+    one chromosome and no positions (pos None)."""
+    from . import genotypes as G
+    if a.zarr is not None:
+        callset = G.open_group(a.zarr, mode="r")
+        try:
+            sites = G.zarr_sites(callset)
+        except KeyError as e:
+            raise SystemExit(f"{prog}: {a.zarr} lacks {e.args[0]}: the LD window needs the variants' CHROM and POS") from None
+        return (np.asarray(callset["calldata/GT"][:], dtype=np.int8), np.asarray(callset["samples"][:]), sites["variants/CHROM"],
+                sites["variants/POS"])
+    if a.vcf is not None:
+        vcf = G.read_vcf(a.vcf, sites=True)
+        return vcf["calldata/GT"], vcf["samples"], vcf["variants/CHROM"], vcf["variants/POS"]
+    gt, samples = read_inputs(a, prog)
+    return gt, samples, None, None
+
+
 def read_locations(sample_data, samples, prog):
     """[N][2] x / y of the genotype samples in their order (NaN = not located); every sample must be in the table."""
     import pandas as pd
@@ -145,18 +175,46 @@ def require_gpu(prog, launch):
         raise SystemExit(f"{prog}: no GPU visible ({launch}); pass --host for the NumPy form")
 
 
-def build_parser(prog, description, own):
-    """The command line of a baseline: inputs, site filter and output stem, then what own(parser) adds, then the device."""
+def add_window_arguments(p):
+    """--ld_window / --ld_window_bp: the window of the ld command and of --ld_prune."""
+    p.add_argument("--ld_window", default=100, type=int, metavar="W",
+                   help="sites after a site that it is compared with (default 100)")
+    p.add_argument("--ld_window_bp", default=None, type=int, metavar="B",
+                   help="also compare only sites at most B base pairs apart (needs positions: not with --matrix)")
+
+
+def check_window(parser, a):
+    """The refusals of a window: a size outside 1 .. LOC_LD_MAX_WINDOW, a negative or positionless base-pair limit."""
+    from ._abi import LOC_LD_MAX_WINDOW
+    if not 1 <= a.ld_window <= LOC_LD_MAX_WINDOW:
+        parser.error(f"--ld_window must be 1 .. {LOC_LD_MAX_WINDOW}")
+    if a.ld_window_bp is not None and a.ld_window_bp < 0:
+        parser.error("--ld_window_bp must be >= 0")
+    if a.ld_window_bp is not None and a.matrix is not None:
+        parser.error("--ld_window_bp needs positions: a --matrix has none")
+
+
+def build_parser(prog, description, own, sample_data=True, prune=True):
+    """The command line of a baseline: inputs, site filter and output stem, then what own(parser) adds, then the device.
+    sample_data False: the command needs no locations, --sample_data is optional; prune: the --ld_prune options."""
     p = argparse.ArgumentParser(prog=prog, description=description)
     p.add_argument("--vcf", default=None, help="VCF (optionally gzipped) with the genotypes")
     p.add_argument("--zarr", default=None, help="zarr-v2 callset with calldata/GT and samples")
     p.add_argument("--matrix", default=None, help="tab-separated count matrix: sampleID, then 0 / 1 / 2 per site")
-    p.add_argument("--sample_data", required=True, help="tab-separated sampleID, x, y; NaN / NA = to be placed")
+    if sample_data:
+        p.add_argument("--sample_data", required=True, help="tab-separated sampleID, x, y; NaN / NA = to be placed")
+    else:
+        p.add_argument("--sample_data", default=None, help="not needed by this command; accepted and not read")
     p.add_argument("--out", required=True, help="output stem")
     p.add_argument("--min_mac", default=2, type=int, help="minimum allele-1 count of a site, as in a fit (default 2)")
     p.add_argument("--max_SNPs", default=None, type=int, help="random subset of sites, drawn as a fit with the same --seed draws it")
     p.add_argument("--seed", default=None, type=int, help="NumPy seed of the --max_SNPs draw")
     own(p)
+    if prune:
+        p.add_argument("--ld_prune", default=None, type=float, metavar="R2",
+                       help="prune the sites first: walking them in input order, a kept site removes every site of its window "
+                            "with r2 above R2 (locator_amd.ld); no default threshold")
+        add_window_arguments(p)
     p.add_argument("--gpu_number", default=None, type=str, help="the GPU to use (sets HIP_VISIBLE_DEVICES)")
     p.add_argument("--silence", default=False, action="store_true", help="no terminal output")
     return p
@@ -167,12 +225,19 @@ def parse_args(parser, argv):
     a = parser.parse_args(argv)
     if sum(v is not None for v in (a.vcf, a.zarr, a.matrix)) != 1:
         parser.error("exactly one of --vcf / --zarr / --matrix must be given")
+    if getattr(a, "ld_prune", None) is not None:
+        if not np.isfinite(a.ld_prune):
+            parser.error("--ld_prune must be a finite r2 threshold")
+        check_window(parser, a)
     return a
 
 
 def prelude(parser, a, launch):
     """Parsed arguments -> (c, P, samples, locs, idx): the count matrix of the sites a fit would train on, its ploidy, the sample
-    IDs, their locations, the site indices.  Without --host and without a GPU it refuses (require_gpu) before anything is read."""
+    IDs, their locations, the site indices.  Without --host and without a GPU it refuses (require_gpu) before anything is read.
+    With --ld_prune the sites are pruned first (ld.prune_sites: in ascending variant index, on the device unless --host); idx
+    keeps its survivors in its own order and a.ld_summary holds the entries the summaries gain.  The site tables are read
+    only then."""
     if a.gpu_number is not None:
         for var in ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
             os.environ[var] = a.gpu_number
@@ -181,10 +246,22 @@ def prelude(parser, a, launch):
     from . import genotypes as G
     if a.seed is not None:
         np.random.seed(a.seed)
-    gt, samples = read_inputs(a, parser.prog)
+    prune = getattr(a, "ld_prune", None) is not None
+    chrom = pos = None
+    if prune:
+        gt, samples, chrom, pos = read_inputs_sites(a, parser.prog)
+    else:
+        gt, samples = read_inputs(a, parser.prog)
     locs = read_locations(a.sample_data, samples, parser.prog)
     _, idx = G.filter_snps(gt, min_mac=a.min_mac, max_snps=a.max_SNPs, verbose=False, sites=True)
     try:
+        if prune:
+            from . import ld
+            idx = np.asarray(idx)
+            kept = ld.prune_sites(gt, idx, chrom, pos, a.ld_prune, a.ld_window, a.ld_window_bp, a.host)
+            a.ld_summary = {"ld_prune": float(a.ld_prune), "ld_window": int(a.ld_window),
+                            "ld_window_bp": None if a.ld_window_bp is None else int(a.ld_window_bp), "K_before_prune": int(len(idx))}
+            idx = idx[np.isin(idx, kept)]
         c, P = count_matrix(gt, idx)
     except ValueError as e:
         raise SystemExit(f"{parser.prog}: {e}") from None

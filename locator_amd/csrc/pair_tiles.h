@@ -1,5 +1,6 @@
 // The tile-pair skeleton of the two all-pairs kernels, ibs_pairs_kernel (ibs_kernels.hip, int8 matrix pipe) and
 // grm_pairs_kernel (grm_kernels.hip, fp32 matrix pipe); arithmetic, LDS image, operand lanes and epilogue stay in their files.
+// ld_band_kernel (ld_kernels.hip) takes the loader, the lanes and the band's pair map from here; its work split is its own.
 // Work split.  The result [n_rows][n_rows] is symmetric, so only the tile pairs (I, J), J >= I, of PT_T = 128 rows a side are
 // computed: grid.x = the pair index, row I of the upper triangle holding tiles - I pairs.  grid.y = the site groups, group g
 // owning the contiguous run of blocks [g per, min(nblocks, (g + 1) per)) of the kernel's site-block width; a group that would
@@ -52,6 +53,12 @@ __device__ __forceinline__ void pt_pair(int pair, int tiles, int& I, int& J) {
     J = I + pair;
 }
 
+// tile pair index -> (I, J) of a band (ld_kernels.hip): every row tile I meets the `per_row` column tiles J = I .. I + per_row - 1
+__device__ __forceinline__ void pt_band_pair(int64_t pair, int per_row, int64_t& I, int64_t& J) {
+    I = pair / per_row;
+    J = I + pair % per_row;
+}
+
 // operand rows within the 128 rows of a side, of wave w's tile tm = 0 / tn = 0 (+ 32 for tile 1), and the lane's half
 __device__ __forceinline__ int pt_arow(int w, int lane) { return 64 * (w >> 1) + (lane & 31); }
 __device__ __forceinline__ int pt_brow(int w, int lane) { return 64 * (w & 1) + (lane & 31); }
@@ -66,6 +73,8 @@ void loc_set_error(const char* fmt, ...);         // api.hip
 
 inline int64_t pt_tiles(int n_rows) { return ((int64_t)n_rows + PT_T - 1) / PT_T; }
 inline int64_t pt_pairs(int64_t tiles) { return tiles * (tiles + 1) / 2; }
+// column tiles a row tile of `tile` rows meets in a band of W following rows: its own .. the one holding its last row + W
+inline int64_t pt_band_tiles(int tile, int W) { return ((int64_t)tile - 1 + W) / tile + 1; }
 
 // The site groups of a launch over `nblocks` site blocks and `pairs` tile pairs: how many are launched and the blocks each
 // owns (0 when there is no block or no pair).  k_groups = 0 chooses from the device: two workgroups fit a compute unit.  Few

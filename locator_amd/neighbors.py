@@ -18,7 +18,9 @@ sample's genetically nearest located samples, and a k-nearest-neighbour placemen
               smallest leave-one-out median error (the smallest such k).
 
 Outputs: {out}_knn_locs.txt (x,y,sampleID as a predlocs file, but NOT named predlocs: it is no replicate),
-{out}_neighbors.txt, {out}_knn_summary.json, with --close T {out}_close_pairs.txt, with --keep_matrix {out}_ibs.npz.  There
+{out}_neighbors.txt, {out}_knn_summary.json, with --close T {out}_close_pairs.txt, with --keep_matrix {out}_ibs.npz.
+--ld_prune R2 (with --ld_window / --ld_window_bp) prunes the sites by linkage disequilibrium first, as locator_amd.ld does; the
+summary then also holds ld_prune, ld_window, ld_window_bp and K_before_prune.  There
 is no silent fallback: without a GPU the run stops and says so; --host asks for the NumPy form, which writes the same bytes.
 """
 from __future__ import annotations
@@ -161,8 +163,9 @@ def placements(nbr, locs):
 
 
 def neighbors(c, P, samples, locs, out=None, k="auto", kmax=32, longlat=False, close=None, keep_matrix=False, host=False,
-              silence=False, device="cuda:0"):
-    """The command's work for a count matrix: returns the summary dict and writes the output files when `out` is given."""
+              silence=False, device="cuda:0", extra=None):
+    """The command's work for a count matrix: returns the summary dict and writes the output files when `out` is given.
+    extra: entries appended to the summary (--ld_prune: what baselines.prelude recorded)."""
     import pandas as pd
     c = B.check_counts(c, P)
     N, K = c.shape
@@ -212,6 +215,7 @@ def neighbors(c, P, samples, locs, out=None, k="auto", kmax=32, longlat=False, c
         pairs = (ia[order], ib[order])
         summary["close"] = float(close)
         summary["n_close_pairs"] = int(len(order))
+    summary.update(extra or {})
 
     lines = [f"{N} samples ({int(located.sum())} located), {K} sites, ploidy {P}",
              f"k = {k_used} ({summary['k_chosen_by']}; leave-one-out median error by k, k = 1 .. {kmax}, smallest at k = {k_auto})",
@@ -277,7 +281,8 @@ def main(argv=None):
         parser.error("--close must be a distance >= 0")
     c, P, samples, locs, _ = B.prelude(parser, a, LAUNCH)
     try:
-        neighbors(c, P, samples, locs, a.out, a.k, a.kmax, a.longlat, a.close, a.keep_matrix, a.host, a.silence)
+        neighbors(c, P, samples, locs, a.out, a.k, a.kmax, a.longlat, a.close, a.keep_matrix, a.host, a.silence,
+                  extra=getattr(a, "ld_summary", None))
     except ValueError as e:
         raise SystemExit(f"{PROG}: {e}") from None
     return 0

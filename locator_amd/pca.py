@@ -29,7 +29,8 @@ much variance the leading axes hold, which axis carries x and which y, and wheth
 
 Outputs: {out}_pca.txt, {out}_pca_eigenvalues.txt, {out}_pca_locs.txt (x,y,sampleID as a predlocs file, but NOT named
 predlocs: it is no replicate), {out}_pca_summary.json, with --keep_matrix {out}_grm.npz, with --loadings
-{out}_pca_loadings.npz.  There is no silent fallback: without a GPU the run stops and says so; --host asks for the NumPy form.
+{out}_pca_loadings.npz.  --ld_prune R2 (with --ld_window / --ld_window_bp) prunes the sites by linkage disequilibrium first,
+as locator_amd.ld does; the summary then also holds ld_prune, ld_window, ld_window_bp and K_before_prune.  There is no silent fallback: without a GPU the run stops and says so; --host asks for the NumPy form.
 
 Unlike neighbors, the device and --host files are NOT byte-identical: the device forms z and sums in fp32, --host in float64.
 They differ by at most what fp32 arithmetic allows: with u = 2^-24, every element |G_dev - G_host| <= (K + 8) u sum_k |z_ik|
@@ -240,8 +241,9 @@ def pc_r2(pcs, locs, located):
 # ---------------------------------------------------------------- the command's work
 
 def pca(c, P, samples, locs, out=None, npc=10, p="auto", longlat=False, loadings=False, keep_matrix=False, host=False,
-        silence=False, device="cuda:0", sites=None):
-    """The command's work for a count matrix: returns the summary dict and writes the output files when `out` is given."""
+        silence=False, device="cuda:0", sites=None, extra=None):
+    """The command's work for a count matrix: returns the summary dict and writes the output files when `out` is given.
+    extra: entries appended to the summary (--ld_prune: what baselines.prelude recorded)."""
     import pandas as pd
     c = B.check_counts(c, P)
     N, K = c.shape
@@ -279,6 +281,7 @@ def pca(c, P, samples, locs, out=None, npc=10, p="auto", longlat=False, loadings
            "eigenvalues": [B.num(v) for v in lam], "variance_share": [B.num(v) for v in share],
            "pc_r2_x": [B.num(v) for v in r2pc[:, 0]], "pc_r2_y": [B.num(v) for v in r2pc[:, 1]]}
     summary = {key: {**shared, **own}[key] for key in SUMMARY_KEYS}
+    summary.update(extra or {})
 
     T = None
     if loadings:
@@ -348,7 +351,8 @@ def main(argv=None):
         parser.error(f"--npc must be 1 .. {NPC_LIMIT}")
     c, P, samples, locs, idx = B.prelude(parser, a, LAUNCH)
     try:
-        pca(c, P, samples, locs, a.out, a.npc, a.p, a.longlat, a.loadings, a.keep_matrix, a.host, a.silence, sites=idx)
+        pca(c, P, samples, locs, a.out, a.npc, a.p, a.longlat, a.loadings, a.keep_matrix, a.host, a.silence, sites=idx,
+            extra=getattr(a, "ld_summary", None))
     except ValueError as e:
         raise SystemExit(f"{PROG}: {e}") from None
     return 0
