@@ -656,7 +656,24 @@ int loc_query_rows(const int8_t* gt, int64_t n_variants, int n_samples, int ploi
  * each split of |A_x|, |A_y|, sqrt(A_x^2 + A_y^2) and J_x^2 + J_y^2, A = D (Xs[i][s] - mov_mean[s]) (Xs: uint8 [n][xs_pitch],
  * one column per site) -> partial[split][4][Ks] fp64.  splits from loc_explain_splits (workgroups to fill compute_units).
  * loc_explain_reduce: out[4][Ks] fp64 = the splits summed in order, divided by n (square root of the fourth: rms_grad).
- * No atomics: bit-identical from run to run.  n <= 2^29; every offset is 64-bit. */
+ * No atomics: bit-identical from run to run.  n <= 2^29; every offset is 64-bit.
+ * Memory (as the Conventions above put it for the training scratch; tests/test_gpu_explain_kernels.py runs all three on
+ * poisoned, guard-banded buffers of exactly these sizes):
+ *   - loc_explain_stack_grad: Hp a multiple of 32 in 32 .. LOC_MAX_WIDTH, L >= 1.  Reads a1 [n][Hp], wh [L-1][Hp][Hp]
+ *     (input-major, as the hidden kernels lie), bh [L-1][Hp], wa [Hp][2], wb [2][2], all zero in H .. Hp.  Writes every
+ *     element of acts ((L-1)*n*Hp floats: acts[l-2] = the ELU output [n][Hp] of layer l = 2 .. L) and of delta1 (2*n*Hp), and
+ *     uses g (2*n*Hp) as scratch: each is written before it is read, so all three may come uninitialised, and nothing beyond
+ *     them is written.  Columns H .. Hp of acts and delta1 come out exactly 0.  With L == 1 acts and g are not touched (NULL);
+ *     with L >= 2 a NULL acts or g is refused.
+ *   - loc_explain_sites: reads delta1 [2n][Hp], U [Ks][Hp], mov_mean [Ks] and the bytes Xs[i * xs_pitch + s], i < n, s < Ks
+ *     (xs_pitch >= Ks; the columns Ks .. xs_pitch are never read).  Writes every element of partial (splits*4*Ks doubles,
+ *     [split][4][Ks]) without reading it first, and nothing beyond.  Split sp holds the sums over the samples
+ *     [64*per*sp, min(n, 64*per*(sp+1))), per = ceil(mt / splits), mt = ceil(2n / 128) M tiles.  A split count is taken iff
+ *     1 <= splits <= min(mt, 65535) and per*(splits - 1) < mt, i.e. no split is left without a tile (mt = 5: 1, 2, 3 and 5,
+ *     not 4); loc_explain_splits returns such a count for every n, Ks and compute_units (1 for n < 1 or Ks < 1), and any
+ *     other accepted count gives the same partial sums per sample range, hence out within 2n * 2^-52 relative.
+ *   - loc_explain_reduce: reads partial [splits][4][Ks], writes every element of out (4*Ks doubles) and nothing beyond.
+ *   - a refused call (-1, the function's name in loc_last_error) launches nothing and writes nothing. */
 int loc_explain_stack_grad(const float* a1, int n, int Hp, int L, const float* wh, const float* bh, const float* wa,
                            const float* wb, float sd_x, float sd_y, float* acts, float* g, float* delta1, void* stream);
 int loc_explain_splits(int n, int Ks, int compute_units);

@@ -1,16 +1,20 @@
 """`python -m locator_amd.explain`, host side: the float64 NumPy form of the per-site Jacobian / attribution against central
 finite differences of the oracle's inference forward, the fold of repeated columns, the window table, and the refusals
-(all before any device work).  Nothing here needs a GPU; tests/test_gpu_explain.py holds the kernels to these forms."""
+(all before any device work); the kernel-level forms of tests/explain_util.py against these, the float32 floor of every case
+of tests/test_gpu_explain_kernels.py, and loc_explain_splits against the launcher's rule.  Nothing here needs a GPU;
+tests/test_gpu_explain.py and tests/test_gpu_explain_kernels.py hold the kernels to these forms."""
 import json
 import os
 
 import numpy as np
 import pytest
 
+from locator_amd import _lib
 from locator_amd import explain as E
 from locator_amd import locator as L
 from locator_amd import query as Q
 from oracle import locator_oracle as O
+from tests import explain_util as XU
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 VCF = os.path.join(GOLD, "test_genotypes.vcf.gz")
@@ -188,3 +192,87 @@ def test_refuse_unknown_samples_and_weights_file(tmp_path):
     L.save_weights(str(tmp_path / "w.weights.npz"), _weights(3))
     with pytest.raises(Q.QueryRefused, match="no site table"):
         E.main(["--model", str(tmp_path / "w.weights.npz"), "--vcf", VCF, "--out", str(tmp_path / "o")])
+
+
+# ------------------------------------------------------------------ the kernel-level forms (tests/explain_util.py)
+def _layer1(p, x):
+    """BatchNorm (inference) and layer 1 exactly as E.reference_delta1 forms them: a1 (n, H), float64."""
+    s = E.bn_scale(p)
+    a = x * s + (p["beta"] - p["mov_mean"] * s)
+    z = a @ p["W"][0] + p["b"][0]
+    return np.where(z > 0, z, np.expm1(np.minimum(z, 0)))
+
+
+@pytest.mark.parametrize("nlayers", [1, 2, 3, 10])
+def test_util_forms_equal_the_package_forms_in_float64(nlayers):
+    """The forms the kernel tests use (from layer 1's output; sums per split, then the reduction) against the forms the
+    command's tests use (from the genotypes; means).  Same operations in the same order: equal bit for bit.  Splitting the
+    samples changes the order of the float64 sums only: 1e-12."""
+    p, x = _toy(K=37, width=16, nlayers=nlayers, n=150, seed=40 + nlayers)
+    K, n = x.shape[1], x.shape[0]
+    want = E.reference_delta1(p, x, LOCS)
+    acts, got = XU.ref_delta1(_layer1(p, x), p["W"][1:nlayers], p["b"][1:nlayers], p["W"][nlayers], p["W"][nlayers + 1],
+                              (LOCS[1], LOCS[3]), np.float64)
+    assert acts.shape == (nlayers - 1, n, 16) and got.dtype == np.float64
+    assert np.array_equal(got, want)
+    U = E.fold_first_layer(p, np.arange(K), K)
+    _, stats = E.reference_stats(want, U, x, p["mov_mean"])
+    xs = x.astype(np.uint8)
+    assert np.array_equal(XU.ref_out(XU.ref_partial(got, U, xs, p["mov_mean"], (0, n), np.float64), n), stats)
+    for splits in XU.accepted_splits(n):                                  # mt = 3: 1, 2, 3
+        parts = [XU.ref_partial(got, U, xs, p["mov_mean"], XU.split_range(n, splits, sp), np.float64)
+                 for sp in range(splits)]
+        np.testing.assert_allclose(XU.ref_out(sum(parts), n), stats, rtol=1e-12, atol=0)
+    assert XU.accepted_splits(n) == [1, 2, 3] and XU.accepted_splits(300) == [1, 2, 3, 5]
+    assert [XU.split_range(300, 3, sp) for sp in range(3)] == [(0, 128), (128, 256), (256, 300)]
+
+
+def test_float32_forms_stay_in_float32():
+    prob = XU.stack_problem(5, 33, 3)
+    acts, d1 = XU.ref_delta1(*[prob[k] for k in ("a1", "Wh", "bh", "wa", "wb", "sd")], np.float32)
+    assert acts.dtype == np.float32 and d1.dtype == np.float32 and acts.shape == (2, 5, 33) and d1.shape == (5, 2, 33)
+    for k in ("a1", "wa", "wb"):
+        assert np.array_equal(prob[k], prob[k].astype(np.float32).astype(np.float64)), k
+
+
+def test_explain_splits_never_returns_a_count_the_launcher_refuses():
+    """loc_explain_splits over n = 1..700, Ks on both sides of the 128-site tile and large, compute units 0 (-> 256), 1, 64,
+    256, 304: 1 <= s <= mt and ceil(mt / s) (s - 1) < mt, the rule by which loc_explain_sites takes a split count."""
+    lib = _lib.load()
+    for cu in (0, 1, 64, 256, 304):
+        for Ks in (1, 127, 128, 129, 5000, 200000):
+            for n in range(1, 701):
+                s = lib.loc_explain_splits(n, Ks, cu)
+                mt = -(-2 * n // 128)
+                assert 1 <= s <= mt and -(-mt // s) * (s - 1) < mt, (n, Ks, cu, s, mt)
+                assert XU.split_accepted(XU.mt_of(n), s) and XU.mt_of(n) == mt
+    # few sites and many tiles: the splits fill the device; many sites: one split
+    assert lib.loc_explain_splits(700, 1, 256) == 11 and lib.loc_explain_splits(700, 200000, 256) == 1
+    assert lib.loc_explain_splits(0, 5, 256) == 1 and lib.loc_explain_splits(-3, 5, 256) == 1
+    assert lib.loc_explain_splits(5, 0, 256) == 1 and lib.loc_explain_splits(5, -1, 256) == 1
+    assert lib.loc_explain_splits(0, 0, 0) == 1
+
+
+@pytest.mark.parametrize("case", XU.STACK_CASES, ids=str)
+def test_floor_of_every_stack_case(case):
+    """The float32 form's distance from the float64 form, per metric: 0 < F and MARGIN F < CAP, so that every case of
+    tests/test_gpu_explain_kernels.py has a bar below what tests/test_gpu_explain.py grants."""
+    _, _, F = XU.stack_refs(XU.stack_problem(*case))
+    assert set(F) == ({"delta1", "acts"} if case[2] > 1 else {"delta1"})
+    for name, f in F.items():
+        assert XU.floor_ok(f, XU.MARGIN_STACK, XU.CAP_STACK), (case, name, f)
+
+
+@pytest.mark.parametrize("case", XU.SITES_CASES, ids=str)
+def test_floor_of_every_sites_case(case):
+    """... for every split count the launcher takes, every split's partial sums and the reduced statistics."""
+    prob = XU.sites_problem(*case)
+    assert prob["X"].max() <= case[3] and (prob["X"].size < 100 or prob["X"].max() == case[3])
+    assert not prob["absent"][0] and (case[1] < 3 or prob["absent"].any())
+    assert not prob["U"][prob["absent"]].any() and prob["U"][~prob["absent"]].any(axis=1).all()
+    for splits in XU.accepted_splits(case[0]):
+        per_split, (_, F_out) = XU.sites_refs(prob, splits)
+        assert len(per_split) == splits
+        assert XU.floor_ok(F_out, XU.MARGIN_STATS, XU.CAP_STATS), (case, splits, F_out)
+        for sp, (_, F) in enumerate(per_split):
+            assert XU.floor_ok(F, XU.MARGIN_STATS, XU.CAP_STATS), (case, splits, sp, F)
