@@ -88,9 +88,14 @@ __global__ __launch_bounds__(GM_HP) void l1_image_kernel(const float* __restrict
             const float* src = w1s + ((int64_t)(kt32 * nht + ht) * 4 + q) * 256 + hi * 128 + c4;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
+#pragma clang fp contract(off)
                 const int kl = (c & 3) * 8 + e, k = kt32 * 32 + kl;
                 const float w = src[kl * 4];
                 csum = fmaf(shift[k], w, csum);
+                // w' = fl32(s_k w), rounded on its own (hence the pragma above).  With contraction allowed the compiler fuses this product with the
+                // first subtraction below into fma(w, s, -hi), and the lower pieces then split the unrounded product - not
+                // the w' that the first piece, l1_rows.hip and the documentation split (tests/test_gpu_l1_infer.py, fixture
+                // A with 2 pieces: one element in 400 differed by a unit of the second piece).
                 float r = w * scale[k];
 #pragma unroll
                 for (int p = 0; p < P; ++p) {
