@@ -51,7 +51,7 @@
 
 // timing ablations (make ablate_chain A=<bits>): results are WRONG with any bit set; they only answer "what does this
 // part of the loop cost".  1 = no barrier, 2 = no per-tile small operands, 4 = no next-forward part, 16 = no Adam
-// arithmetic, 32 = no weight stores
+// arithmetic, 32 = no weight stores, 64 = no trailing tail workgroups (the hidden layers and heads are not updated)
 #ifndef LOC_CHAIN_ABLATE
 #define LOC_CHAIN_ABLATE 0
 #endif
@@ -142,42 +142,53 @@ __global__ __launch_bounds__(512) void l1_bwd_adam_chain_kernel(
         gload16_uniform<2048, (NTM & 2) != 0>(wq[2], w1s, o); gload16_uniform<2048, (NTM & 1) != 0>(mq[2], m1s, o); gload16_uniform<2048, (NTM & 1) != 0>(vq[2], v1s, o);
         gload16_uniform<3072, (NTM & 2) != 0>(wq[3], w1s, o); gload16_uniform<3072, (NTM & 1) != 0>(mq[3], m1s, o); gload16_uniform<3072, (NTM & 1) != 0>(vq[3], v1s, o);
     };
-    // The first unit is requested before anything else; the prologue ends with vmcnt(0).
+    // ---- Prologue: ONE drain of the memory pipe (round 8).  Everything the first two super-tiles need is requested back to
+    // back, untracked and unconditional like the loop's loads, and the first unit's burst (96 KB per workgroup, every
+    // workgroup of the launch at once) is waited for exactly once, with nothing dependent behind it:
+    //   RPW      row indices: a loader lane reads ITS row of rows / rows_next itself (role r's lane needs row pc >> 2 only)
+    //   NDZ      dZ, element t + 512 j of [NR][Hp]
+    //   12       the first unit                                         (load_unit)
+    //   -- vm_wait<12>: the RPW + NDZ small requests in front of the unit have landed (a lone round trip; the unit streams
+    //      in meanwhile) --
+    //   3 RPW    small operands of super-tile T0           -> ld        (addresses from the row indices in registers)
+    //   3 RPW    small operands of super-tile T0 + G       -> ld2       (prologue-only words, moved into ld once landed)
+    //   dZ and the row lists go to LDS, two LDS-only barriers, the column sums of dZ: all under the unit's burst
+    //   -- vm_wait_unit<0>: the unit, ld, ld2 --   stage(0, T0), ld = ld2, one LDS-only barrier
+    // No thread reads another thread's GLOBAL writes here, so every barrier is lds_barrier().  Largest number of requests a
+    // wave has in flight: RPW + NDZ + 12 = 45 (width 512), 46 (two row blocks), then 12 + 6 RPW = 36 (width 64): below
+    // vmcnt's 63.  The loop's first vm_wait_unit<12> comes behind the first step's own 12 requests with NOTHING older in
+    // flight (the drain above), so its count holds as in every later step.
+    constexpr int NDZ = NR * Hp / 512;           // dZ words per thread
+    static_assert(NR * Hp % 512 == 0, "dZ staging: whole words per thread");
     f32x4 wA[4], mA[4], vA[4], wB[4], mB[4], vB[4];
-    load_unit(ktile((int)blockIdx.x, kq), ut0, wA, mA, vA);
-
-    if constexpr (RB == 1) {
-        for (int i = t; i < 32 * Hp; i += 512) dzl[(i / Hp) * PZ + (i % Hp)] = dz1[i];
-    } else {
-        // the stack kernel carries (and zeroes beyond n_b) the rows of the 32-row blocks IN USE only: a short last minibatch
-        // leaves the other block's dZ rows stale
-        const int n_used = 32 * ((n_b + 31) / 32);
-        for (int i = t; i < NR * Hp; i += 512) dzl[(i / Hp) * PZ + (i % Hp)] = (i / Hp) < n_used ? dz1[i] : 0.f;
-    }
-    if (t < NR) {
-        rows_l[t] = t < n_b ? rows[t] : 0;
-        rown_l[t] = (chain && t < n_b_next) ? rows_next[t] : 0;
-    }
-    __syncthreads();
-
-    // dzsum[h] = sum_b dZ[b][h] for this lane's 16 units h = w*32 + rowmap(r, hi): column sums through `red` (free until
-    // the loop; the barriers below separate the two uses), then registers for the whole kernel
-    if (t < Hp) {
-        float sum = 0.f;
-#pragma unroll 8
-        for (int b = 0; b < NR; ++b) sum += dzl[b * PZ + t];
-        red[t] = sum;
-    }
-    __syncthreads();
-    // (every width but 256 re-reads them from LDS at each use instead: two unit tiles per wave would need 32 registers, and the
-    // narrow widths' extra loader-role words already spill without the 16)
-    float dzs_r[16];
-    if constexpr (DZS_REG) {
+    uint32_t prow[RPW], dzr[NDZ];
+    // is there a row index for role w + 8 rr to read (a genotype kind, an entry inside its minibatch), and where?  (Wave-uniform
+    // kind, per-lane entry.)  No: row 0, the `t < n_b ? rows[t] : 0` rule.
+    auto row_entry = [&](int rr, bool& cur, int* entry = nullptr) {
+        const int role = w + 8 * rr, slot = role / NK, kind = role - NK * slot;
+        cur = kind < 2 * RB;
+        const int e = ((kind & (2 * RB - 1)) * 64 + lane) >> 2;
+        if (entry) *entry = e;
+        return role < NROLE && kind < 4 * RB && (cur ? e < n_b : (chain && e < n_b_next));
+    };
 #pragma unroll
-        for (int r = 0; r < 16; ++r) dzs_r[r] = red[ut0 * 32 + rowmap(r, hi)];
-    } else {
-        if (t < Hp) dzs_l[t] = red[t];
+    for (int rr = 0; rr < RPW; ++rr) {
+        bool cur;
+        int e;
+        const void* a = alpha_tab + w;           // "nothing to fetch": one read-only word per wave
+        if (row_entry(rr, cur, &e)) a = (cur ? rows : rows_next) + e;
+        gload4_fresh(prow[rr], a);
     }
+    // (two row blocks: the stack kernel carries, and zeroes beyond n_b, the rows of the 32-row blocks IN USE only: a short last
+    // minibatch leaves the other block's dZ rows stale, so they are not read and count as zero)
+    const int n_used = RB == 1 ? 32 : 32 * ((n_b + 31) / 32);
+#pragma unroll
+    for (int j = 0; j < NDZ; ++j) {
+        const int i = t + 512 * j;
+        const void* a = (RB == 1 || i / Hp < n_used) ? (const void*)(dz1 + i) : (const void*)(alpha_tab + w);
+        gload4_fresh(dzr[j], a);
+    }
+    load_unit(ktile((int)blockIdx.x, kq), ut0, wA, mA, vA);
 
     // gamma (lanes 0..31) or beta (lanes 32..63) of SNP jl of the tile: one Adam per lane.  beta / m_beta / v_beta sit Kp
     // floats behind gamma / m_gamma / v_gamma (loc_param_layout; checked by the launcher): one wave-uniform base each
@@ -190,7 +201,9 @@ __global__ __launch_bounds__(512) void l1_bwd_adam_chain_kernel(
     uint32_t ld[RPW][3];
 #pragma unroll
     for (int rr = 0; rr < RPW; ++rr) ld[rr][0] = ld[rr][1] = ld[rr][2] = 0u;
-    auto fetch = [&](int T) {
+    // (row_of(rr, this minibatch?, entry): the row index - from the LDS lists in the loop, from the lane's own register in the
+    // prologue, where the lists are not staged yet)
+    auto fetch_to = [&](uint32_t (&dst)[RPW][3], int T, auto row_of) {
         // three 4-byte loads per role and lane, ALWAYS; the role (and "nothing to fetch") only chooses the addresses
 #pragma unroll
         for (int rr = 0; rr < RPW; ++rr) {
@@ -202,7 +215,7 @@ __global__ __launch_bounds__(512) void l1_bwd_adam_chain_kernel(
             if (kt >= 0) {
                 if (kind < 4 * RB) {
                     const int pc = (kind & (2 * RB - 1)) * 64 + lane;  // 8-byte piece of the [NR rows][32 bytes] tile
-                    const int row = kind < 2 * RB ? rows_l[pc >> 2] : rown_l[pc >> 2];   // (no next minibatch: row 0, unused)
+                    const int row = row_of(rr, kind < 2 * RB, pc >> 2);                    // (no next minibatch: row 0, unused)
                     const uint8_t* a = X + (int64_t)row * pitch + (int64_t)ktc * KT + 8 * (pc & 3);
                     a0 = a; a1 = a + 4; a2 = a;
                 } else if (kind == 4 * RB) {
@@ -213,9 +226,10 @@ __global__ __launch_bounds__(512) void l1_bwd_adam_chain_kernel(
                     a0 = next_stats + (int64_t)hi * Kp + k; a1 = a0; a2 = a0;
                 }
             }
-            gload4_fresh(ld[rr][0], a0); gload4_fresh(ld[rr][1], a1); gload4_fresh(ld[rr][2], a2);
+            gload4_fresh(dst[rr][0], a0); gload4_fresh(dst[rr][1], a1); gload4_fresh(dst[rr][2], a2);
         }
     };
+    auto fetch = [&](int T) { fetch_to(ld, T, [&](int, bool cur, int e) { return cur ? rows_l[e] : rown_l[e]; }); };
     auto stage = [&](int buf, int T) {
 #pragma unroll
         for (int rr = 0; rr < RPW; ++rr) {
@@ -247,15 +261,61 @@ __global__ __launch_bounds__(512) void l1_bwd_adam_chain_kernel(
             }
         }
     };
+    // (every width but 256 re-reads the column sums of dZ from LDS at each use: two unit tiles per wave would need 32 registers,
+    // and the narrow widths' extra loader-role words already spill without the 16)
+    float dzs_r[16];
+    vm_wait<12>();                                              // the row indices and dZ; the first unit stays in flight
     {
         const int T0 = blockIdx.x;
-        fetch(T0);
-        vm_wait_unit<0>(wA, mA, vA, ld);
+#pragma unroll
+        for (int rr = 0; rr < RPW; ++rr) vm_landed(prow[rr]);
+#pragma unroll
+        for (int j = 0; j < NDZ; ++j) vm_landed(dzr[j]);
+#pragma unroll
+        for (int rr = 0; rr < RPW; ++rr) {
+            bool cur;
+            if (!row_entry(rr, cur)) prow[rr] = 0u;
+        }
+        auto row_reg = [&](int rr, bool, int) { return (int)prow[rr]; };
+        uint32_t ld2[RPW][3];
+        fetch_to(ld, T0, row_reg);
+        fetch_to(ld2, T0 + G, row_reg);                         // staged during the first iteration
+        // the row lists in LDS (the loop's fetch reads them there) come from the genotype loader lanes of slot 0: roles
+        // 0 .. 4 RB - 1, four lanes per entry
+#pragma unroll
+        for (int rr = 0; rr < RPW; ++rr) {
+            const int role = w + 8 * rr;
+            if (role < 4 * RB) (role < 2 * RB ? rows_l : rown_l)[((role & (2 * RB - 1)) * 64 + lane) >> 2] = (int)prow[rr];
+        }
+#pragma unroll
+        for (int j = 0; j < NDZ; ++j) {
+            const int i = t + 512 * j;
+            dzl[(i / Hp) * PZ + (i % Hp)] = (RB == 1 || i / Hp < n_used) ? bitsf(dzr[j]) : 0.f;
+        }
+        lds_barrier();
+        // dzsum[h] = sum_b dZ[b][h] for this lane's 16 units h = w*32 + rowmap(r, hi): column sums through `red` (free until
+        // the loop; the barriers separate the two uses), then registers for the whole kernel
+        if (t < Hp) {
+            float sum = 0.f;
+#pragma unroll 8
+            for (int b = 0; b < NR; ++b) sum += dzl[b * PZ + t];
+            red[t] = sum;
+        }
+        lds_barrier();
+        if constexpr (DZS_REG) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dzs_r[r] = red[ut0 * 32 + rowmap(r, hi)];
+        } else {
+            if (t < Hp) dzs_l[t] = red[t];
+        }
+        vm_wait_unit<0>(wA, mA, vA, ld);                        // the one drain: the first unit and both sets of small operands
+#pragma unroll
+        for (int rr = 0; rr < RPW; ++rr) { vm_landed(ld2[rr][0]); vm_landed(ld2[rr][1]); vm_landed(ld2[rr][2]); }
         stage(0, T0);
-        fetch(T0 + G);                                          // staged during the first iteration
-        vm_wait_unit<0>(wA, mA, vA, ld);
+#pragma unroll
+        for (int rr = 0; rr < RPW; ++rr) { ld[rr][0] = ld2[rr][0]; ld[rr][1] = ld2[rr][1]; ld[rr][2] = ld2[rr][2]; }
     }
-    __syncthreads();
+    lds_barrier();
 
     // bias of layer 1: db1[h] = sum_b dZ[b][h]   (workgroup 0, the waves of slot 0: wave <-> unit tile)
     if (blockIdx.x == 0 && kq == 0) {
@@ -542,6 +602,9 @@ int l1_chain_launch(const uint8_t* X, int64_t x_pitch, const int32_t* rows, int 
         ta = *tail;
         n_tail = (tail->L - 1) * nht * nht + 1;
     }
+#if LOC_CHAIN_ABLATE & 64
+    n_tail = 0;
+#endif
     const int ntm = !tune || tune->l1b_nt_mask == 0 ? 13 : (tune->l1b_nt_mask < 0 ? 0 : tune->l1b_nt_mask);
 #define LAUNCH_CHAIN_NR(M, N, R)                                                                                   \
     {                                                                                                              \

@@ -55,3 +55,23 @@ for it in range(its):
     tot += np.median(d, axis=0)
 print("median cycles per phase over the launch:", [int(v) for v in tot], " sum", int(tot.sum()))
 print("whole loop per wave:", (s[:, its - 1, 7] - s[:, 0, 0]).tolist())
+
+# The launch's two ends (round 8): stamps outside the loop as (cycle counter, 100 MHz wall clock) per wave, and the first / last
+# instruction of the first and of the last trailing tail workgroup.  CHAIN_END_NAMES: the points of another source (the parent's).
+END_NAMES = os.environ.get("CHAIN_END_NAMES", "kernel entry|row indices + dZ landed: vm_wait<12>|barrier 1 (dZ, row lists in LDS)|"
+                           "barrier 2 (column sums)|the one drain: unit A, ld, ld2|barrier 3 (tile 0 staged)|loop entry|"
+                           "loop left, last requests drained|last store (partial sums)").split("|")
+ends = (C.c_ulonglong * (8 * 16 * 2))()
+tail = (C.c_ulonglong * 8)()
+assert lib.loc_debug_chain_end_stamps(ends, tail) == 0
+e = np.array(ends[:], dtype=np.uint64).reshape(8, 16, 2).astype(np.int64)
+tl = np.array(tail[:], dtype=np.uint64).reshape(2, 2, 2).astype(np.int64)
+c0, w0 = e[:, 0, 0].min(), e[:, 0, 1].min()
+print("ends of the launch, cycles since the workgroup's first wave entered (min..max over its 8 waves) | wall clock, us")
+for i, name in enumerate(END_NAMES):
+    print(f"  {i} {name:55s} {int((e[:, i, 0] - c0).min()):8d}..{int((e[:, i, 0] - c0).max()):8d} | "
+          f"{(e[:, i, 1] - w0).min() / 100:8.2f}..{(e[:, i, 1] - w0).max() / 100:8.2f}")
+for which, name in ((0, "first"), (1, "last")):
+    if tl[which, 0, 0]:
+        print(f"  {name} tail workgroup: {int(tl[which, 1, 0] - tl[which, 0, 0])} cycles; wall clock {(tl[which, 0, 1] - w0) / 100:.2f} .. "
+              f"{(tl[which, 1, 1] - w0) / 100:.2f} us after the stamped workgroup's entry")
