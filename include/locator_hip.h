@@ -478,12 +478,22 @@ int loc_l1_backward_adam_chain(const uint8_t* X, int64_t x_pitch, const int32_t*
                                const float* alpha_tab, int alpha_tab_len, const float* lr, const int* t_base, int t_off,
                                int grid, float* partial, int64_t partial_floats, const loc_tuning* tune, void* stream);
 
-/* ---- hidden Dense(width, elu) layers + Dropout (locator.py:319-323) ---- */
+/* ---- hidden Dense(width, elu) layers + Dropout (locator.py:319-323) ----
+ * One 32-row block per launch.  Hp: a multiple of 32 in 32..LOC_MAX_WIDTH; anything else, and a NULL mandatory pointer, is
+ * refused with an error before any launch (tests/test_gpu_stack_layers.py).  Activations are [32][Hp], kernels [Hp][Hp]
+ * (input unit x output unit), biases [Hp]; units H..Hp are padding: zero in every input, left exactly zero in every output.
+ * out = ELU(in W + b): ALL 32 rows of `in` are read and ALL 32 rows of `out` are written, whatever the batch holds, so the
+ * rows of `in` beyond the batch have to be readable (their values only reach the same rows of `out`).  mask [32][Hp] keep
+ * flags non-NULL: out_drop = out * (mask ? keep_scale : 0) as well, all 32 rows; mask NULL: out_drop is not touched. */
 int loc_dense_forward(const float* in, const float* W, const float* b, int Hp, float* out, float* out_drop,
                       const uint8_t* mask, float keep_scale, void* stream);
 /* One backward launch: (a) dz_prev = (dz W^T) * dropmask * ELU'(a_prev);
  * (b) optionally dW/db + Adam for ANOTHER layer `W2` (the one above), whose old
- * weights are no longer needed.  Either half may be skipped with NULL pointers. */
+ * weights are no longer needed.  Either half may be skipped with NULL pointers: a half is given in full - (a) dz, W,
+ * a_prev, dz_prev, its mask optional; (b) in2, dz2, W2, mW2, vW2, b2, mb2, vb2 - or not at all, and the skipped half
+ * writes nothing.  (a) reads and writes all 32 rows.  (b) contracts all 32 rows of in2 and dz2: rows >= n_b of dz2 have to
+ * be EXACTLY 0 (loc_head_train and (a) leave them so) and rows >= n_b of in2 finite - then their values change no result.
+ * Hp as for loc_dense_forward. */
 int loc_dense_backward(const float* dz, const float* W, const float* a_prev, const uint8_t* mask,
                        float keep_scale, float* dz_prev, const float* in2, const float* dz2, float* W2,
                        float* mW2, float* vW2, float* b2, float* mb2, float* vb2, int Hp,
@@ -491,12 +501,17 @@ int loc_dense_backward(const float* dz, const float* W, const float* a_prev, con
                        int t_off, void* stream);
 
 /* ---- Dense(2), Dense(2), euclidean_distance_loss (locator.py:314-315, :324-325) ---- */
-/* Training: loss (batch mean, to *loss_out), head gradients + Adam, dz_last = dA * ELU'(a). */
+/* Training: loss (batch mean, to *loss_out), head gradients + Adam, dz_last = dA * ELU'(a).  1 <= n_b <= 32, Hp a multiple
+ * of 32 in 32..LOC_MAX_WIDTH (else an error before any launch).  a [32][Hp]: rows >= n_b are read and have to be finite
+ * (they meet a zero gradient; their values change no result); dz_last [32][Hp] is written whole, rows >= n_b EXACTLY 0.
+ * m / v: the flat moment buffers, written only at off_wa (2 * Hp values), off_ba (2), off_wb (4) and off_bb (2).  A sample
+ * at distance 0 from its target adds a zero gradient (Keras: NaN). */
 int loc_head_train(const float* a, int Hp, int n_b, const int32_t* rows, const float* Y, float* wa, float* ba,
                    float* wb, float* bb, float* m, float* v, int64_t off_wa, int64_t off_ba, int64_t off_wb,
                    int64_t off_bb, float* dz_last, float* loss_out, const float* alpha_tab, int alpha_tab_len,
                    const float* lr, const int* t_base, int t_off, void* stream);
-/* Inference: yhat[b][0..1]; if rows/Y non-NULL also dist[b] = ||yhat - Y[rows[b]]||. */
+/* Inference: yhat[b][0..1]; if rows/Y non-NULL also dist[b] = ||yhat - Y[rows[b]]||.  n_b and Hp as for loc_head_train.
+ * Rows >= n_b of `a` are read (any value) and rows >= n_b of yhat / dist are NOT written; dist NULL: no distances. */
 int loc_head_eval(const float* a, int Hp, int n_b, const float* wa, const float* ba, const float* wb,
                   const float* bb, float* yhat, const int32_t* rows, const float* Y, float* dist, void* stream);
 

@@ -186,7 +186,7 @@ __global__ __launch_bounds__(DENSE_THREADS) void dense_bwd_kernel(
 
 // ---------------------------------------------------------------------------------------------
 // Dense(2) -> Dense(2) -> euclidean_distance_loss, backward, Adam on the head, and
-// dz_last[b][k] = dA[b][k] * ELU'(a[b][k]).  One block of 256 threads.
+// dz_last[b][k] = dA[b][k] * ELU'(a[b][k]).  One block of 512 threads.
 // Loss gradient at d == 0 is taken as 0 (Keras: NaN) — the one intentional deviation.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(512) void head_train_kernel(const float* __restrict__ a, int Hp, int n_b,
@@ -336,8 +336,21 @@ __global__ __launch_bounds__(256) void head_eval_kernel(const float* __restrict_
 // ---------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------
+// Every launcher refuses before its launch: the kernels index with Hp = 32 * NHT, so a width that is no multiple of 32
+// would run the next smaller kernel on buffers of another pitch.
+static bool stack_width_ok(const char* who, int Hp) {
+    if (Hp >= 32 && Hp <= LOC_MAX_WIDTH && Hp % 32 == 0) return true;
+    loc_set_error("%s: Hp=%d is no multiple of 32 in 32..%d", who, Hp, LOC_MAX_WIDTH);
+    return false;
+}
+
 extern "C" int loc_dense_forward(const float* in, const float* W, const float* b, int Hp, float* out,
                                  float* out_drop, const uint8_t* mask, float keep_scale, void* stream) {
+    if (!stack_width_ok("loc_dense_forward", Hp)) return -1;
+    if (!in || !W || !b || !out || (mask && !out_drop)) {
+        loc_set_error("loc_dense_forward: null buffer (in, W, b and out are mandatory, out_drop with a mask)");
+        return -1;
+    }
     const int nht = Hp / 32;
 #define LAUNCH(N)                                                                                           \
     hipLaunchKernelGGL(dense_fwd_kernel<N>, dim3(N), dim3(DENSE_THREADS), 0, (hipStream_t)stream, in, W, b, out, \
@@ -353,6 +366,22 @@ extern "C" int loc_dense_backward(const float* dz, const float* W, const float* 
                                   float* mW2, float* vW2, float* b2, float* mb2, float* vb2, int Hp,
                                   const float* alpha_tab, int alpha_tab_len, const float* lr, const int* t_base,
                                   int t_off, void* stream) {
+    if (!stack_width_ok("loc_dense_backward", Hp)) return -1;
+    const int dx_given = (dz != nullptr) + (W != nullptr) + (a_prev != nullptr) + (dz_prev != nullptr);
+    const int dw_given = (in2 != nullptr) + (dz2 != nullptr) + (W2 != nullptr) + (mW2 != nullptr) + (vW2 != nullptr) +
+                         (b2 != nullptr) + (mb2 != nullptr) + (vb2 != nullptr);
+    if ((dx_given != 0 && dx_given != 4) || (dx_given == 0 && mask)) {
+        loc_set_error("loc_dense_backward: the dx half takes dz, W, a_prev and dz_prev (mask optional), all or none");
+        return -1;
+    }
+    if (dw_given != 0 && dw_given != 8) {
+        loc_set_error("loc_dense_backward: the dW half takes in2, dz2, W2, mW2, vW2, b2, mb2 and vb2, all or none");
+        return -1;
+    }
+    if (dw_given && (!alpha_tab || alpha_tab_len < 1 || !lr || !t_base)) {
+        loc_set_error("loc_dense_backward: the dW half needs alpha_tab (alpha_tab_len >= 1), lr and t_base");
+        return -1;
+    }
     const int nht = Hp / 32;
     const int n_dx = dz_prev ? nht : 0;
     const int n_dw = W2 ? nht * nht : 0;
@@ -373,6 +402,7 @@ extern "C" int loc_head_train(const float* a, int Hp, int n_b, const int32_t* ro
                               const float* alpha_tab, int alpha_tab_len, const float* lr, const int* t_base,
                               int t_off, void* stream) {
     if (n_b < 1 || n_b > LOC_ROWS) { loc_set_error("loc_head_train: n_b=%d out of 1..32", n_b); return -1; }
+    if (!stack_width_ok("loc_head_train", Hp)) return -1;
     const size_t hlds = ((size_t)32 * (Hp + 1) + 2 * Hp) * sizeof(float);
     LOC_ENSURE_LDS(head_train_kernel, hlds);
     hipLaunchKernelGGL(head_train_kernel, dim3(1), dim3(512), hlds, (hipStream_t)stream, a, Hp, n_b, rows, Y, wa, ba,
@@ -386,6 +416,7 @@ extern "C" int loc_head_eval(const float* a, int Hp, int n_b, const float* wa, c
                              const float* bb, float* yhat, const int32_t* rows, const float* Y, float* dist,
                              void* stream) {
     if (n_b < 1 || n_b > LOC_ROWS) { loc_set_error("loc_head_eval: n_b=%d out of 1..32", n_b); return -1; }
+    if (!stack_width_ok("loc_head_eval", Hp)) return -1;
     hipLaunchKernelGGL(head_eval_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a, Hp, n_b, wa, ba, wb, bb,
                        yhat, rows, Y, dist);
     LOC_CHECK_LAUNCH();
