@@ -635,7 +635,9 @@ int loc_l1_forward_gemm_i8_packed(const uint8_t* X2, int64_t x2_pitch, const int
  * pos = exclusive prefix sum of keep, *n_kept = their number (the SNP count K of the window's model).
  * loc_filter_snps_rows: X[r][pos[v]] = number of allele-1 copies of sample sample_order[r] at kept variant v
  * (to_allele_counts()[:, :, 1] transposed and row-gathered: `ac[:, rows].T`), r < n_out; X is [n_out][x_pitch] uint8 and must
- * be zeroed beyond K by the caller.  No --impute_missing / --max_SNPs here (both consume the NumPy stream: host path). */
+ * be zeroed beyond K by the caller: the rows kernels write columns [0, K) of rows whose sample_order[r] is in 0..n_samples-1
+ * and nothing else (a row with any other sample_order[r] is skipped).  n_variants <= 2^31 - 1024 everywhere (pos is int32);
+ * n_out == 0 launches nothing.  No --impute_missing / --max_SNPs here (both consume the NumPy stream: host path). */
 int loc_filter_snps_flags(const int8_t* gt, int64_t n_variants, int n_samples, int ploidy, int min_mac, uint8_t* keep,
                           int32_t* pos, int32_t* n_kept, void* stream);
 int loc_filter_snps_rows(const int8_t* gt, int64_t n_variants, int n_samples, int ploidy, const uint8_t* keep,

@@ -131,7 +131,7 @@ extern "C" int loc_filter_snps_flags(const int8_t* gt, int64_t n_variants, int n
 extern "C" int loc_filter_snps_rows(const int8_t* gt, int64_t n_variants, int n_samples, int ploidy, const uint8_t* keep,
                                     const int32_t* pos, const int32_t* sample_order, int n_out, uint8_t* X, int64_t x_pitch,
                                     void* stream) {
-    if (n_variants < 1 || n_samples < 1 || ploidy < 1 || n_out < 0) {
+    if (n_variants < 1 || n_samples < 1 || ploidy < 1 || n_out < 0 || n_variants > ((int64_t)1 << 31) - 1024) {   // pos is int32
         loc_set_error("loc_filter_snps_rows: n_variants=%lld n_samples=%d ploidy=%d n_out=%d", (long long)n_variants, n_samples,
                       ploidy, n_out);
         return -1;

@@ -803,7 +803,7 @@ def count_alleles(gt, max_allele=None):
         max_allele = int(gt.max()) if gt.size else 0
     max_allele = max(max_allele, 0)
     out = np.zeros((gt.shape[0], max_allele + 1), np.int32)
-    flat = gt.reshape(gt.shape[0], -1)
+    flat = gt.reshape(gt.shape[0], int(np.prod(gt.shape[1:])))       # not -1: no variant at all is a valid input
     for a in range(max_allele + 1):
         out[:, a] = np.count_nonzero(flat == a, axis=1)
     return out

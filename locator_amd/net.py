@@ -537,7 +537,10 @@ def filter_snps_device(gt, sample_order, min_mac=2, return_keep=False):
     _lib.check(lib.loc_filter_snps_flags(_ptr(gt), V, N, P, int(min_mac), _ptr(keep), _ptr(pos), _ptr(nk), _stream()),
                "loc_filter_snps_flags")
     K = int(nk.item())
-    order = torch.as_tensor(np.asarray(sample_order, dtype=np.int32)).to(dev)
+    order = np.asarray(sample_order, dtype=np.int32)
+    if len(order) and (int(order.min()) < 0 or int(order.max()) >= N):       # the kernel would skip the row: all zero
+        raise ValueError(f"sample_order holds rows outside 0..{N - 1}")
+    order = torch.as_tensor(order).to(dev)
     Kp = (max(K, 1) + 31) // 32 * 32
     X = torch.zeros((len(order), Kp), dtype=torch.uint8, device=dev)
     if K > 0:

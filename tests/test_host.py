@@ -1094,6 +1094,38 @@ def test_native_host_filter_and_transposes_equal_the_numpy_restatement():
     assert G.filter_snps(v, 2, verbose=False).shape[0] == 5830
 
 
+def test_native_host_filter_at_the_allele_mask_words_and_the_min_mac_bounds():
+    """csrc/codecs.c loc_snp_flags keeps two 64-bit allele masks (alleles 0..63 | 64..127): every ordered pair of alleles on
+    both sides of a word edge, one bit position in two words, three alleles over three words, every missing code, and
+    allele-1 counts on both sides of min_mac (tests/filter_util.py), as haploid, diploid and triploid calls.  The same
+    sites, the same matrix as the NumPy spelling; the reference of the device tests (flags_ref) is pinned to it here too."""
+    from tests import filter_util as FU
+    flat = np.concatenate([FU.allele_edge_cases(66), FU.mac_boundary_cases(66, (1, 2, 3))])
+    for P in (1, 2, 3):
+        gt = FU.as_calls(flat, P)
+        kept = []
+        for mm in (1, 2, 3):
+            keep, _, K = FU.check_flags_ref(gt, mm)
+            ref, ref_idx = G.filter_snps(gt, mm, verbose=False, native=False, sites=True)
+            got, got_idx = G.filter_snps(gt, mm, verbose=False, native=True, sites=True)
+            assert np.array_equal(got_idx, ref_idx), (P, mm, np.setxor1d(got_idx, ref_idx)[:8])
+            assert got.dtype == ref.dtype and got.shape == ref.shape and np.array_equal(got, ref), (P, mm)
+            assert 0 < K < len(gt)
+            kept.append(K)
+        assert kept[0] > kept[1] >= kept[2], kept                            # the allele-1 count filter bites from 2 on
+    # a pair over the C code's word edge is kept only if BOTH words are read: alleles 63 | 64, 0 | 127, 64 | 127
+    for a, b in ((63, 64), (0, 127), (64, 127), (1, 65)):
+        site = np.array([[a] * 5 + [b]], np.int8).reshape(1, 3, 2)
+        assert len(G.filter_snps(site, 1, verbose=False, native=True)) == 1, (a, b)
+    # a window without a biallelic site: 0 SNPs either way (the NumPy spelling once failed on the empty array it filters next)
+    mono = np.zeros((7, 4, 2), np.int8)
+    mono[::2] = 1
+    for mm in (1, 2):
+        for native in (False, True):
+            ac, idx = G.filter_snps(mono, mm, verbose=False, native=native, sites=True)
+            assert ac.shape == (0, 4) and ac.dtype == np.int8 and len(idx) == 0, (mm, native)
+
+
 def test_worker_gpu_binding_maps_the_parents_visible_list_and_counting_gpus_needs_no_torch(monkeypatch, tmp_path):
     """replicates._bind_worker_to_gpu (one process per GPU through HIP_VISIBLE_DEVICES): worker g of a
     parent that sees everything gets "g"; of a parent restricted by --gpu_number / HIP_VISIBLE_DEVICES the g-th entry of that
