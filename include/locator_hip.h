@@ -527,12 +527,27 @@ int loc_stack_forward_backward(const float* a1_in, const float* Wh, const float*
                                const uint8_t* mask, float keep_scale, int Hp, int L, int n_pre, int n_b,
                                int slot_rows, const int32_t* rows, const float* Y, float* acts, float* adrop,
                                float* dz, float* head_out, const loc_tuning* tune, void* stream);
-/* Inference counterpart: layers 2..L + heads for n_b rows (any n_b; a1 is [n_b][Hp]); yhat[n_b][2], optional dist[n_b]. */
+/* Inference counterpart: layers 2..L + heads for n_b rows; yhat[n_b][2], optional dist[n_b].  The contract of
+ * loc_stack_forward_eval, loc_stack_forward_eval_form and loc_stack_forward_eval_partial (tests/test_gpu_stack_eval.py calls
+ * all three, in every form, on guarded buffers of exactly these sizes):
+ *   - a1 is [n_b][Hp] and exactly that is read: no form touches a row at or past n_b (the vector-ALU forms stage row
+ *     n_b - 1 again for the rows of their last group that do not exist).  Units H..Hp of a1, Wh, bh and wa are zero.
+ *   - yhat [n_b][2] is written for every row; nothing beyond it.
+ *   - dist [n_b] is written only when it is non-NULL AND targets are given (rows and Y non-NULL): no dist without targets,
+ *     as loc_head_eval.  rows [n_b] indexes Y [..][2]; both are given or both are NULL.
+ *   - refused with -1 and the entry point's name in loc_last_error, before any launch and with nothing written: n_b < 0,
+ *     L < 2, an Hp other than 64 / 128 / 256 / 512, Y without rows or rows without Y, a NULL operand; for
+ *     loc_stack_forward_eval_partial also groups < 1, group_stride < n_b * Hp and a NULL partial / cvec8 / b1.
+ *   - n_b = 0 returns 0, launches nothing and writes nothing. */
 int loc_stack_forward_eval(const float* a1, const float* Wh, const float* bh, const float* wa, const float* ba,
                            const float* wb, const float* bb, int Hp, int L, int n_b, const int32_t* rows,
                            const float* Y, float* yhat, float* dist, void* stream);
 /* loc_stack_forward_eval whose layer-1 activations are still the many-row GEMM's group partial sums
- * (loc_l1_forward_gemm_i8_partial): a1[m][h] = ELU(sum_g partial[g * group_stride + m * Hp + h] + sum_s cvec8[s * Hp + h] + b1[h]). */
+ * (loc_l1_forward_gemm_i8_partial): a1[m][h] = ELU(sum_g partial[g * group_stride + m * Hp + h] + sum_s cvec8[s * Hp + h] + b1[h]),
+ * in l1_gemm_reduce_kernel's association (four quarters of (groups + 3) / 4 groups, each summed in ascending order,
+ * ((q0 + q1) + q2) + q3, then + ((cvec8[0] + ... + cvec8[7]) + b1)): the same bits as the dedicated reduction, in each of the three
+ * kernels.  Of every group only rows < n_b are read: group_stride may exceed n_b * Hp (loc_predict: n_b rounded up to 128
+ * rows) with anything in between. */
 int loc_stack_forward_eval_partial(const float* partial, int groups, int64_t group_stride, const float* cvec8,
                                    const float* b1, const float* Wh, const float* bh, const float* wa, const float* ba,
                                    const float* wb, const float* bb, int Hp, int L, int n_b, const int32_t* rows,
@@ -544,7 +559,8 @@ int loc_stack_forward_eval_partial(const float* partial, int groups, int64_t gro
  * units rows).  rows_form (loc_stack_forward_eval_form /
  * loc_stack_forward_eval_partial; loc_tuning.stack_rows in loc_predict): 0 = by row count, 1 = always the 32-row form where
  * supported, 2 = always the 16-row form, -1 / -2 / -3 = 2 / 4 / 8 rows per workgroup on the vector ALU.  Same arithmetic, different summation order: predictions agree to fp32
- * round-off (tests/test_gpu_stack_rows.py). */
+ * round-off (tests/test_gpu_stack_rows.py, tests/test_gpu_stack_eval.py: bit for bit on all-integer stacks, within a measured multiple of
+ * the float32 reference's own error on random ones). */
 int loc_stack_rows_supported(int Hp, int L);
 int loc_stack_rows_min_rows(void);
 int loc_stack_forward_eval_form(const float* a1, const float* Wh, const float* bh, const float* wa, const float* ba,

@@ -259,7 +259,12 @@ __global__ __launch_bounds__(SF_THREADS) void stack_fused_kernel(
         for (int o = 0; o < NO; ++o) {
             const int i = t + SF_THREADS * o;
             a1v[o] = 0.f;
-            if (stage && i < R * Hp) gload4_inout(a1v[o], a1_in + (int64_t)(r0 + i / Hp) * Hp + i % Hp);
+            // inference: a1 is [n_b][Hp] and nothing beyond it is read - the rows of the last group past n_b (their results are
+            // dropped) stage row n_b - 1 again.  The load itself stays unconditional: a predicate that is uniform over a row
+            // could take a whole wave's load away.  The training launch carries every row of its 32-row blocks.
+            int sr = r0 + i / Hp;
+            if constexpr (!TRAIN) sr = sr < n_b ? sr : n_b - 1;
+            if (stage && i < R * Hp) gload4_inout(a1v[o], a1_in + (int64_t)sr * Hp + i % Hp);
         }
         if (has_y) gload4_inout(yrow, rows + r0 + t);
         gload4_inout(h_wa0, wa + 2 * (t % Hp));
@@ -365,7 +370,7 @@ __global__ __launch_bounds__(SF_THREADS) void stack_fused_kernel(
                 ho[0] = d; ho[1] = dy10; ho[2] = dy11; ho[3] = y10; ho[4] = y11; ho[5] = g0; ho[6] = g1; ho[7] = 0.f;
             } else if (valid) {
                 yhat[2 * b] = y20; yhat[2 * b + 1] = y21;
-                if (dist) dist[b] = d;
+                if (dist && Y != nullptr) dist[b] = d;      // no dist without targets (as loc_head_eval and stack_rows.hip)
             }
         }
         lds_barrier();
@@ -539,15 +544,22 @@ extern "C" int loc_stack_forward_backward(const float* a1_in, const float* Wh, c
 static int sf_eval_launch(const float* a1, const float* rd_partial, int rd_G, int64_t rd_MH, const float* rd_cvec8,
                           const float* rd_b1, const float* Wh, const float* bh, const float* wa, const float* ba,
                           const float* wb, const float* bb, int Hp, int L, int n_b, const int32_t* rows, const float* Y,
-                          float* yhat, float* dist, void* stream, int rows_form = 0) {
+                          float* yhat, float* dist, void* stream, const char* who, int rows_form = 0) {
     // rows_form: 0 = by row count (width 256: 2, 4 or 8 rows per workgroup on the vector ALU while one round of workgroups
     // covers the rows, above 8 x compute units rows 16 or 32 rows per workgroup on the fp32 matrix pipe, stack_rows.hip: the
     // measured round times are there); 1 = always the 32-row matrix-pipe form (where supported), 2 = always the 16-row form;
     // -1 = always 2 rows per workgroup on the vector ALU, -2 = 4 rows, -3 = 8 rows (measurement / tests)
-    if (L < 2) {        // the kernel has at least one layer pass (the labels and the ring are waited for inside the passes)
-        loc_set_error("hidden stack of a predict: L=%d (needs at least one hidden layer pass)", L);
+    // Refused on the host, before any launch (tests/test_gpu_stack_eval.py): L < 2 - the kernel has at least one layer pass (the
+    // labels and the ring are waited for inside the passes); a width without a fused form; n_b < 0; targets without their row
+    // indices or the reverse - every form would follow the one pointer it has on the device.
+    if (L < 2 || !loc_stack_fused_supported(Hp) || n_b < 0 || (rows == nullptr) != (Y == nullptr) || !yhat ||
+        (!a1 && !rd_partial) || !Wh || !bh || !wa || !ba || !wb || !bb) {
+        loc_set_error("%s: Hp=%d (64/128/256/512 after padding) L=%d (>= 2) n_b=%d (>= 0) rows=%s Y=%s (both or neither)%s", who, Hp,
+                      L, n_b, rows ? "given" : "NULL", Y ? "given" : "NULL",
+                      yhat && (a1 || rd_partial) && Wh && bh && wa && ba && wb && bb ? "" : ", a NULL operand");
         return -1;
     }
+    if (n_b == 0) return 0;      // nothing to do: no launch (the vector-ALU grid would hold warm-up helpers only)
     if (rows_form >= 0 && loc_stack_rows_supported(Hp, L) && (rows_form > 0 || n_b >= loc_stack_rows_min_rows()))
         return sr_eval_launch(a1, rd_partial, rd_G, rd_MH, rd_cvec8, rd_b1, Wh, bh, wa, ba, wb, bb, L, n_b, rows, Y, yhat, dist,
                               rows_form == 1 ? 32 : rows_form == 2 ? 16 : 0, stream);
@@ -588,14 +600,15 @@ static int sf_eval_launch(const float* a1, const float* rd_partial, int rd_G, in
 extern "C" int loc_stack_forward_eval(const float* a1, const float* Wh, const float* bh, const float* wa,
                                       const float* ba, const float* wb, const float* bb, int Hp, int L, int n_b,
                                       const int32_t* rows, const float* Y, float* yhat, float* dist, void* stream) {
-    return sf_eval_launch(a1, nullptr, 0, 0, nullptr, nullptr, Wh, bh, wa, ba, wb, bb, Hp, L, n_b, rows, Y, yhat, dist, stream);
+    return sf_eval_launch(a1, nullptr, 0, 0, nullptr, nullptr, Wh, bh, wa, ba, wb, bb, Hp, L, n_b, rows, Y, yhat, dist, stream,
+                          "loc_stack_forward_eval");
 }
 extern "C" int loc_stack_forward_eval_form(const float* a1, const float* Wh, const float* bh, const float* wa,
                                            const float* ba, const float* wb, const float* bb, int Hp, int L, int n_b,
                                            const int32_t* rows, const float* Y, float* yhat, float* dist, int rows_form,
                                            void* stream) {
     return sf_eval_launch(a1, nullptr, 0, 0, nullptr, nullptr, Wh, bh, wa, ba, wb, bb, Hp, L, n_b, rows, Y, yhat, dist, stream,
-                          rows_form);
+                          "loc_stack_forward_eval_form", rows_form);
 }
 
 extern "C" int loc_stack_forward_eval_partial(const float* partial, int groups, int64_t group_stride, const float* cvec8,
@@ -608,7 +621,7 @@ extern "C" int loc_stack_forward_eval_partial(const float* partial, int groups, 
         return -1;
     }
     return sf_eval_launch(nullptr, partial, groups, group_stride, cvec8, b1, Wh, bh, wa, ba, wb, bb, Hp, L, n_b, rows, Y, yhat,
-                          dist, stream, rows_form);
+                          dist, stream, "loc_stack_forward_eval_partial", rows_form);
 }
 
 extern "C" int loc_stack_dw_adam_tail(int Hp, int L, int n_pre, int n_b, int slot_rows, int use_drop, const float* acts,

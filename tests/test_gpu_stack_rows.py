@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from oracle import locator_oracle as O
-from tests.gpu_util import build_net, make_problem, maxerr
+from tests.gpu_util import build_net, guarded, make_problem, maxerr
 
 pytestmark = pytest.mark.gpu
 
@@ -54,8 +54,12 @@ def test_matrix_pipe_form_equals_the_vector_alu_form_and_the_oracle(n, width, nl
     net = build_net(x, y, p)
     assert net.lib.loc_stack_rows_supported(net.d.Hp, net.d.L)
     a1 = _a1(p, x)
-    a1_dev = torch.zeros(((n + 127) // 128 * 128, net.d.Hp), device="cuda")
-    a1_dev[:n, :width] = torch.from_numpy(a1.astype(np.float32)).cuda()
+    # a1 is [n][Hp] and exactly that is read (include/locator_hip.h; tests/test_gpu_stack_eval.py): a guarded view of n * Hp
+    # floats with a NaN pattern directly above it, not a zero-filled buffer rounded up to 128 rows
+    a1_flat, a1_margins = guarded(n * net.d.Hp, torch.float32, 128 * net.d.Hp)
+    a1_dev = a1_flat.view(n, net.d.Hp)
+    a1_dev.zero_()
+    a1_dev[:, :width] = torch.from_numpy(a1.astype(np.float32)).cuda()
     ref = _rest(p, a1.astype(np.float32).astype(np.float64))
     got_m, dist_m = _run(net, a1_dev, n, form, True)
     got_v, dist_v = _run(net, a1_dev, n, -1, True)
@@ -76,6 +80,7 @@ def test_matrix_pipe_form_equals_the_vector_alu_form_and_the_oracle(n, width, nl
         if n <= 2048:
             got_d, _ = _run(net, a1_dev, n, 0, True)
             assert np.array_equal(got_d, got_v)
+    a1_margins("a1")
 
 
 def test_only_width_256_takes_the_matrix_pipe_form():
