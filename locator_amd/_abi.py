@@ -4,7 +4,8 @@ package restates the header.  include/locator_hip_query.h (later entry points) i
 include/locator_hip_regions.h (the regions command): REGION_PROTOTYPES and its LOC_REGION_* constants, and
 include/locator_hip_neighbors.h (the neighbors command): NEIGHBOR_PROTOTYPES and its LOC_IBS_* constants, and
 include/locator_hip_pca.h (the pca command): PCA_PROTOTYPES and its LOC_PCA_* constants, and
-include/locator_hip_ld.h (the ld command): LD_PROTOTYPES and its LOC_LD_* constants.  No torch here: locator_amd.genotypes and the command line import this module before torch.
+include/locator_hip_ld.h (the ld command): LD_PROTOTYPES and its LOC_LD_* constants, and
+include/locator_hip_spa.h (the spa command): SPA_PROTOTYPES and its LOC_SPA_* constants.  No torch here: locator_amd.genotypes and the command line import this module before torch.
 
 The reader knows the header's spelling, not C: one declaration per `;`, scalar types from _SCALARS, comments only as
 /* */.  Anything else raises with the offending text, so that a header edit cannot silently drop or mis-type an entry."""
@@ -24,6 +25,8 @@ NEIGHBOR_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_neighbors.h
 PCA_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_pca.h")
 # the ld command's entry point (locator_amd/ld.py): functions and LOC_LD_* integer constants only
 LD_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_ld.h")
+# the spa command's entry points (locator_amd/spa.py): functions and LOC_SPA_* integer constants only
+SPA_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_spa.h")
 
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
             "float": C.c_float, "double": C.c_double}
@@ -145,3 +148,12 @@ if (_structs or set(LD_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES) | se
         or not all(k.startswith("LOC_LD_") and isinstance(v, int) for k, v in LD_CONSTANTS.items())):
     raise ValueError(f"{LD_HEADER} may declare new functions and LOC_LD_* integer constants only")
 globals().update(LD_CONSTANTS)
+if not os.path.exists(SPA_HEADER):
+    raise FileNotFoundError(f"{SPA_HEADER} not found: it declares the entry points of the spa command")
+with open(SPA_HEADER) as _f:
+    SPA_CONSTANTS, _structs, SPA_PROTOTYPES = parse(_f.read())
+if (_structs or set(SPA_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES) | set(REGION_PROTOTYPES) | set(NEIGHBOR_PROTOTYPES)
+                                       | set(PCA_PROTOTYPES) | set(LD_PROTOTYPES))
+        or not all(k.startswith("LOC_SPA_") and isinstance(v, int) for k, v in SPA_CONSTANTS.items())):
+    raise ValueError(f"{SPA_HEADER} may declare new functions and LOC_SPA_* integer constants only")
+globals().update(SPA_CONSTANTS)

@@ -93,9 +93,10 @@ def num(v):
     return None if v is None or not np.isfinite(v) else float(v)
 
 
-def placement_summary(c, P, located, xy, locs, longlat, method):
+def placement_summary(c, P, located, xy, locs, longlat, method, how="leave-one-out"):
     """(entries, lines) every baseline reports about its chosen placement xy [N][2]: the summary entries N, n_located, K, P,
-    error_unit, r2_x, r2_y, mean_error, median_error (the command fixes the key order) and the terminal lines of R2 and error."""
+    error_unit, r2_x, r2_y, mean_error, median_error (the command fixes the key order) and the terminal lines of R2 and error.
+    how: what the located samples' placements are (spa: "held-out", its folds are no leave-one-out)."""
     err = errors(xy[located], locs[located], longlat)
     ok = ~np.isnan(err)
     fitted, truth = xy[located][ok], locs[located][ok]
@@ -104,8 +105,8 @@ def placement_summary(c, P, located, xy, locs, longlat, method):
     entries = {"N": int(c.shape[0]), "n_located": int(located.sum()), "K": int(c.shape[1]), "P": int(P), "error_unit": unit,
                "r2_x": num(r[0]), "r2_y": num(r[1]), "mean_error": num(np.mean(err[ok])) if ok.any() else None,
                "median_error": num(np.median(err[ok])) if ok.any() else None}
-    lines = [f"R2(x)={r[0]}", f"R2(y)={r[1]}", f"mean {method} leave-one-out error {entries['mean_error']}",
-             f"median {method} leave-one-out error {entries['median_error']} ({unit})"]
+    lines = [f"R2(x)={r[0]}", f"R2(y)={r[1]}", f"mean {method} {how} error {entries['mean_error']}",
+             f"median {method} {how} error {entries['median_error']} ({unit})"]
     return entries, lines
 
 
