@@ -5,7 +5,8 @@ include/locator_hip_regions.h (the regions command): REGION_PROTOTYPES and its L
 include/locator_hip_neighbors.h (the neighbors command): NEIGHBOR_PROTOTYPES and its LOC_IBS_* constants, and
 include/locator_hip_pca.h (the pca command): PCA_PROTOTYPES and its LOC_PCA_* constants, and
 include/locator_hip_ld.h (the ld command): LD_PROTOTYPES and its LOC_LD_* constants, and
-include/locator_hip_spa.h (the spa command): SPA_PROTOTYPES and its LOC_SPA_* constants.  No torch here: locator_amd.genotypes and the command line import this module before torch.
+include/locator_hip_spa.h (the spa command): SPA_PROTOTYPES and its LOC_SPA_* constants, and
+include/locator_hip_admix.h (the admix command): ADMIX_PROTOTYPES and its LOC_ADMIX_* constants.  No torch here: locator_amd.genotypes and the command line import this module before torch.
 
 The reader knows the header's spelling, not C: one declaration per `;`, scalar types from _SCALARS, comments only as
 /* */.  Anything else raises with the offending text, so that a header edit cannot silently drop or mis-type an entry."""
@@ -27,6 +28,8 @@ PCA_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_pca.h")
 LD_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_ld.h")
 # the spa command's entry points (locator_amd/spa.py): functions and LOC_SPA_* integer constants only
 SPA_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_spa.h")
+# the admix command's entry points (locator_amd/admix.py): functions and LOC_ADMIX_* integer constants only
+ADMIX_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_admix.h")
 
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
             "float": C.c_float, "double": C.c_double}
@@ -157,3 +160,12 @@ if (_structs or set(SPA_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES) | s
         or not all(k.startswith("LOC_SPA_") and isinstance(v, int) for k, v in SPA_CONSTANTS.items())):
     raise ValueError(f"{SPA_HEADER} may declare new functions and LOC_SPA_* integer constants only")
 globals().update(SPA_CONSTANTS)
+if not os.path.exists(ADMIX_HEADER):
+    raise FileNotFoundError(f"{ADMIX_HEADER} not found: it declares the entry points of the admix command")
+with open(ADMIX_HEADER) as _f:
+    ADMIX_CONSTANTS, _structs, ADMIX_PROTOTYPES = parse(_f.read())
+if (_structs or set(ADMIX_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES) | set(REGION_PROTOTYPES) | set(NEIGHBOR_PROTOTYPES)
+                                         | set(PCA_PROTOTYPES) | set(LD_PROTOTYPES) | set(SPA_PROTOTYPES))
+        or not all(k.startswith("LOC_ADMIX_") and isinstance(v, int) for k, v in ADMIX_CONSTANTS.items())):
+    raise ValueError(f"{ADMIX_HEADER} may declare new functions and LOC_ADMIX_* integer constants only")
+globals().update(ADMIX_CONSTANTS)

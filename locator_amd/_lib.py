@@ -31,7 +31,8 @@ def use_library(path):
 # point needs its prototype there (since version 1 of the ABI: in include/locator_hip_query.h, EXT_SIGNATURES; the regions
 # command's: include/locator_hip_regions.h, REGION_SIGNATURES; the neighbors command's: include/locator_hip_neighbors.h,
 # NEIGHBOR_SIGNATURES; the pca command's: include/locator_hip_pca.h, PCA_SIGNATURES; the ld command's:
-# include/locator_hip_ld.h, LD_SIGNATURES; the spa command's: include/locator_hip_spa.h, SPA_SIGNATURES) and nothing here.
+# include/locator_hip_ld.h, LD_SIGNATURES; the spa command's: include/locator_hip_spa.h, SPA_SIGNATURES; the admix command's:
+# include/locator_hip_admix.h, ADMIX_SIGNATURES) and nothing here.
 Dims, Layout, Tuning, Net, CbState = (_abi.STRUCTS[n] for n in ("loc_dims", "loc_layout", "loc_tuning", "loc_net",
                                                                 "loc_cb_state"))
 SIGNATURES = _abi.PROTOTYPES
@@ -41,6 +42,7 @@ NEIGHBOR_SIGNATURES = _abi.NEIGHBOR_PROTOTYPES
 PCA_SIGNATURES = _abi.PCA_PROTOTYPES
 LD_SIGNATURES = _abi.LD_PROTOTYPES
 SPA_SIGNATURES = _abi.SPA_PROTOTYPES
+ADMIX_SIGNATURES = _abi.ADMIX_PROTOTYPES
 
 
 class LocatorHipError(RuntimeError):
@@ -61,7 +63,7 @@ def load():
             "or `make -C locator_amd/csrc`.  locator_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **REGION_SIGNATURES, **NEIGHBOR_SIGNATURES,
-                              **PCA_SIGNATURES, **LD_SIGNATURES, **SPA_SIGNATURES}.items():
+                              **PCA_SIGNATURES, **LD_SIGNATURES, **SPA_SIGNATURES, **ADMIX_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -195,9 +195,10 @@ def check_window(parser, a):
         parser.error("--ld_window_bp needs positions: a --matrix has none")
 
 
-def build_parser(prog, description, own, sample_data=True, prune=True):
+def build_parser(prog, description, own, sample_data=True, prune=True, sample_data_help=None):
     """The command line of a baseline: inputs, site filter and output stem, then what own(parser) adds, then the device.
-    sample_data False: the command needs no locations, --sample_data is optional; prune: the --ld_prune options."""
+    sample_data False: the command needs no locations, --sample_data is optional (sample_data_help: what it does with them when
+    they are given; prelude then returns locs None without them); prune: the --ld_prune options."""
     p = argparse.ArgumentParser(prog=prog, description=description)
     p.add_argument("--vcf", default=None, help="VCF (optionally gzipped) with the genotypes")
     p.add_argument("--zarr", default=None, help="zarr-v2 callset with calldata/GT and samples")
@@ -205,7 +206,7 @@ def build_parser(prog, description, own, sample_data=True, prune=True):
     if sample_data:
         p.add_argument("--sample_data", required=True, help="tab-separated sampleID, x, y; NaN / NA = to be placed")
     else:
-        p.add_argument("--sample_data", default=None, help="not needed by this command; accepted and not read")
+        p.add_argument("--sample_data", default=None, help=sample_data_help or "not needed by this command; accepted and not read")
     p.add_argument("--out", required=True, help="output stem")
     p.add_argument("--min_mac", default=2, type=int, help="minimum allele-1 count of a site, as in a fit (default 2)")
     p.add_argument("--max_SNPs", default=None, type=int, help="random subset of sites, drawn as a fit with the same --seed draws it")
@@ -235,7 +236,7 @@ def parse_args(parser, argv):
 
 def prelude(parser, a, launch):
     """Parsed arguments -> (c, P, samples, locs, idx): the count matrix of the sites a fit would train on, its ploidy, the sample
-    IDs, their locations, the site indices.  Without --host and without a GPU it refuses (require_gpu) before anything is read.
+    IDs, their locations (None when the command's --sample_data is optional and was not given), the site indices.  Without --host and without a GPU it refuses (require_gpu) before anything is read.
     With --ld_prune the sites are pruned first (ld.prune_sites: in ascending variant index, on the device unless --host); idx
     keeps its survivors in its own order and a.ld_summary holds the entries the summaries gain.  The site tables are read
     only then."""
@@ -253,7 +254,7 @@ def prelude(parser, a, launch):
         gt, samples, chrom, pos = read_inputs_sites(a, parser.prog)
     else:
         gt, samples = read_inputs(a, parser.prog)
-    locs = read_locations(a.sample_data, samples, parser.prog)
+    locs = None if a.sample_data is None else read_locations(a.sample_data, samples, parser.prog)
     _, idx = G.filter_snps(gt, min_mac=a.min_mac, max_snps=a.max_SNPs, verbose=False, sites=True)
     try:
         if prune:
