@@ -234,12 +234,12 @@ def parse_args(parser, argv):
     return a
 
 
-def prelude(parser, a, launch):
+def prelude(parser, a, launch, sites=False):
     """Parsed arguments -> (c, P, samples, locs, idx): the count matrix of the sites a fit would train on, its ploidy, the sample
     IDs, their locations (None when the command's --sample_data is optional and was not given), the site indices.  Without --host and without a GPU it refuses (require_gpu) before anything is read.
     With --ld_prune the sites are pruned first (ld.prune_sites: in ascending variant index, on the device unless --host); idx
     keeps its survivors in its own order and a.ld_summary holds the entries the summaries gain.  The site tables are read
-    only then."""
+    only then, or with sites=True (localpca), which appends the CHROM and POS of idx to the answer (None, None for a --matrix)."""
     if a.gpu_number is not None:
         for var in ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
             os.environ[var] = a.gpu_number
@@ -250,7 +250,7 @@ def prelude(parser, a, launch):
         np.random.seed(a.seed)
     prune = getattr(a, "ld_prune", None) is not None
     chrom = pos = None
-    if prune:
+    if prune or sites:
         gt, samples, chrom, pos = read_inputs_sites(a, parser.prog)
     else:
         gt, samples = read_inputs(a, parser.prog)
@@ -267,4 +267,7 @@ def prelude(parser, a, launch):
         c, P = count_matrix(gt, idx)
     except ValueError as e:
         raise SystemExit(f"{parser.prog}: {e}") from None
+    if sites:
+        at = np.asarray(idx, dtype=np.int64)
+        return c, P, samples, locs, idx, None if chrom is None else np.asarray(chrom)[at], None if pos is None else np.asarray(pos)[at]
     return c, P, samples, locs, idx

@@ -24,6 +24,9 @@
 // slabs of an element in group order in double and writes g[i][j] (i <= j) and its copy g[j][i], inside a diagonal tile too:
 // no floating-point atomics, the same bits on every launch, G exactly symmetric.
 //
+// grm_windows_kernel (the localpca command, include/locator_hip_localpca.h) is the same block loop with a window of sites on
+// grid.y in place of the site group and an epilogue of its own: its text stands before it.
+//
 // pca_loadings_kernel: t[v][p] = sum_s z[s][v] u[s][p].  Memory-bound (one pass over c), so vector-ALU: a workgroup owns
 // LOC_PCA_SITES = 256 sites, lane l four consecutive ones (one dword of c per row), wave w the components 16 w .. 16 w + 15,
 // 64 accumulators a thread; u is staged through LDS 64 rows at a time, zero-padded to 64 columns, and read as broadcasts.
@@ -31,6 +34,7 @@
 #include "pair_tiles.h"
 
 #include "../../include/locator_hip_pca.h"
+#include "../../include/locator_hip_localpca.h"
 
 #include <cstdint>
 
@@ -166,6 +170,136 @@ __global__ __launch_bounds__(256) void grm_reduce_kernel(const float* __restrict
     g[j * n_rows + i] = s;
 }
 
+// mean or scale of 16 sites, 0 for a site outside the window: the window holds the sites lo <= e < hi of the 16
+__device__ __forceinline__ void gw_mask_sites(f32x4 (&v)[4], int lo, int hi) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int x = 0; x < 4; ++x) v[e][x] = (4 * e + x >= lo && 4 * e + x < hi) ? v[e][x] : 0.f;
+}
+
+// grm_windows_kernel (include/locator_hip_localpca.h): grm_pairs_kernel's block loop with the window on grid.y in place of
+// the site group.  The workgroup walks the absolute blocks v0 / 32 .. (v1 - 1) / 32 of its window, so every piece it reads is
+// an aligned 16-byte piece wherever the window starts; in the first and the last block the sites outside [v0, v1) get
+// mean = scale = 0 in registers: z = fl(fl((float)c - 0) * 0) = +0 for a call, 0 for a missing one.
+// Epilogue: one workgroup holds the window's whole sum, so the tile goes straight to g[w] as fp32 - no slab, no reduce pass.
+// An element with i <= j is stored from its register, lanes 0 .. 31 of a store covering 128 consecutive bytes of row i.  Its
+// copy g[w][j][i] would leave the registers as 32 rows x 4 bytes per store, so each wave turns its 32 x 32 tiles through its
+// own quarter of the operand LDS (free after the loop; rows of 33 floats: no bank is hit twice by a half wave) and stores the
+// copy along row j, 128 consecutive bytes a half wave again.  -DGW_MIRROR_STRIDED (measurement builds only: `make variant`)
+// stores the copy from the registers instead.  A diagonal tile pair takes the same path, i < j selecting the copy: no element
+// is stored from two different registers.
+constexpr int GW_TR = 33;                         // floats of a row of a wave's transposition image
+static_assert(32 * GW_TR <= 2 * GR_SIDE / (GR_NT / 64), "a wave's 32 x 33 image fits its quarter of the operand LDS");
+
+__global__ __launch_bounds__(GR_NT) void grm_windows_kernel(const int8_t* __restrict__ c, int n_rows, int64_t K, int64_t pitch,
+                                                            const float* __restrict__ mean, const float* __restrict__ scale,
+                                                            int tiles, const int64_t* __restrict__ win, float* __restrict__ g) {
+    __shared__ __attribute__((aligned(16))) float lds[2 * GR_SIDE];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    int I, J;
+    pt_pair((int)blockIdx.x, tiles, I, J);
+    const bool diag = I == J;
+    const int64_t v0 = min(max(win[2 * (int64_t)blockIdx.y], (int64_t)0), K);
+    const int64_t v1 = min(max(win[2 * (int64_t)blockIdx.y + 1], v0), K);
+    const int64_t b0 = v0 / GR_B;
+    const int64_t b1 = v1 > v0 ? (v1 - 1) / GR_B + 1 : b0;       // an empty window walks no block
+
+    float* const side_i = lds;
+    float* const side_j = diag ? lds : lds + GR_SIDE;
+    const int64_t row_i0 = (int64_t)I * GR_T, row_j0 = (int64_t)J * GR_T;
+    const int srow = t >> 1, schunk = t & 1;
+
+    uint4 raw_i = make_uint4(~0u, ~0u, ~0u, ~0u), raw_j = make_uint4(~0u, ~0u, ~0u, ~0u);
+    f32x4 mv[4], sv[4];
+    auto request = [&](int64_t b) {
+        const int64_t k = b * GR_B + 16 * schunk;
+        raw_i = pt_load_piece(c, row_i0 + srow, n_rows, k, K, pitch);
+        if (!diag) raw_j = pt_load_piece(c, row_j0 + srow, n_rows, k, K, pitch);
+        gr_load_sites(mean, k, K, mv);
+        gr_load_sites(scale, k, K, sv);
+        if (k < v0 || k + 16 > v1) {              // the window's first or last block only
+            const int lo = (int)min(max(v0 - k, (int64_t)0), (int64_t)16), hi = (int)min(max(v1 - k, (int64_t)0), (int64_t)16);
+            gw_mask_sites(mv, lo, hi);
+            gw_mask_sites(sv, lo, hi);
+        }
+    };
+
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+
+    const int arow = pt_arow(w, lane), brow = pt_brow(w, lane), half = pt_half(lane);
+    if (b0 < b1) request(b0);
+    for (int64_t b = b0; b < b1; ++b) {
+        gr_store_piece(side_i, srow, schunk, raw_i, mv, sv);
+        if (!diag) gr_store_piece(side_j, srow, schunk, raw_j, mv, sv);
+        __syncthreads();
+        if (b + 1 < b1) request(b + 1);
+#pragma unroll
+        for (int s = 0; s < GR_B / 8; ++s) {
+            const int piece = 2 * s + half;
+            f32x4 a[2], bb[2];
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) {
+                a[tt] = *reinterpret_cast<const f32x4*>(side_i + gr_at(arow + 32 * tt, piece));
+                bb[tt] = *reinterpret_cast<const f32x4*>(side_j + gr_at(brow + 32 * tt, piece));
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+                    for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = mfma32(a[tm][q], bb[tn][q], acc[tm][tn]);
+        }
+        __syncthreads();                          // the block is consumed: the next one, or the epilogue, may overwrite it
+    }
+
+    float* const gw = g + (int64_t)blockIdx.y * n_rows * (int64_t)n_rows;
+    float* const tr = lds + w * (2 * GR_SIDE / (GR_NT / 64));
+    const int64_t ld = n_rows;                    // wave-uniform: the row offsets below are scalar
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn) {
+            const int64_t i00 = row_i0 + 64 * (w >> 1) + 32 * tm, j00 = row_j0 + 64 * (w & 1) + 32 * tn;
+            // element r of the tile: row i0 + rowmap(r, 0), column j
+            const int64_t i0 = i00 + 4 * half, j = j00 + (lane & 31);
+            const int64_t room = j < n_rows ? j - i0 : -1;                            // rows 0 .. room of this lane have i <= j
+            float* const direct = gw + i0 * ld + j;
+#ifdef GW_MIRROR_STRIDED
+            float* const copy = gw + j * ld + i0;
+#endif
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                if (rowmap(r, 0) <= room) direct[rowmap(r, 0) * ld] = acc[tm][tn][r];  // i <= j < n_rows
+#ifdef GW_MIRROR_STRIDED
+                if (rowmap(r, 0) < room) copy[rowmap(r, 0)] = acc[tm][tn][r];
+#else
+                tr[(lane & 31) * GW_TR + rowmap(r, half)] = acc[tm][tn][r];           // [column of the tile][row of the tile]
+#endif
+            }
+#ifndef GW_MIRROR_STRIDED
+            __syncthreads();
+            // element rr of the turned tile: row j00 + half + 2 rr of g, column im
+            const int64_t im = i00 + (lane & 31), jm0 = j00 + half;
+            const int64_t rows = min((int64_t)n_rows, jm0 + 32) - jm0;                // rows jm0 + 2 rr below n_rows: 2 rr < rows
+            const int64_t first = im - jm0;                                           // ... and past im: 2 rr > first
+            float* const copy = gw + jm0 * ld + im;
+#pragma unroll
+            for (int rr = 0; rr < 16; ++rr) {
+                const float v = tr[(2 * rr + half) * GW_TR + (lane & 31)];
+                if (2 * rr < rows && 2 * rr > first) copy[2 * rr * ld] = v;           // im < jm < n_rows
+            }
+            __syncthreads();                      // the image is read: the next tile may overwrite it
+#endif
+        }
+}
+
 constexpr int PL_NT = 256;
 constexpr int PL_ROWS = 64;                       // rows of u per stage
 constexpr int PL_PW = 16;                         // components per wave
@@ -276,6 +410,31 @@ extern "C" int loc_grm_pairs(const int8_t* c, int n_rows, int64_t K, int64_t pit
     }
     hipLaunchKernelGGL(grm_reduce_kernel, dim3((unsigned)pairs, GR_T * GR_T / 256), dim3(256), 0, (hipStream_t)stream,
                        (const float*)work, (int)groups, n_rows, (int)tiles, g);     // no group: every sum is 0
+    LOC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int loc_grm_windows(const int8_t* c, int n_rows, int64_t K, int64_t pitch, const float* mean, const float* scale,
+                               const int64_t* win, int n_windows, float* g, void* stream) {
+    if (!gr_sizes_ok("loc_grm_windows", n_rows, K, 0) || !pt_sizes_ok("loc_grm_windows", n_rows, K, pitch, 0, 0)) return -1;
+    if (n_windows < 1 || n_windows > LOC_LOCALPCA_MAX_WINDOWS) {
+        loc_set_error("loc_grm_windows: n_windows=%d (1..%d: the caller batches above that)", n_windows, LOC_LOCALPCA_MAX_WINDOWS);
+        return -1;
+    }
+    if (!g || !win || (K > 0 && (!c || !mean || !scale))) {
+        loc_set_error("loc_grm_windows: null buffer");
+        return -1;
+    }
+    if (K > 0 && !pt_rows_aligned("loc_grm_windows", c, pitch)) return -1;
+    if ((uintptr_t)g % 4 != 0 || (uintptr_t)win % 16 != 0 || (K > 0 && ((uintptr_t)mean % 16 != 0 || (uintptr_t)scale % 16 != 0))) {
+        loc_set_error("loc_grm_windows: mean, scale and win must be multiples of 16 bytes (site constants and window bounds are "
+                      "read 16 bytes at a time), g of 4");
+        return -1;
+    }
+    if (n_rows == 0) return 0;
+    const int64_t tiles = pt_tiles(n_rows), pairs = pt_pairs(tiles);
+    hipLaunchKernelGGL(grm_windows_kernel, dim3((unsigned)pairs, (unsigned)n_windows), dim3(GR_NT), 0, (hipStream_t)stream, c,
+                       n_rows, K, pitch, mean, scale, (int)tiles, win, g);
     LOC_CHECK_LAUNCH();
     return 0;
 }

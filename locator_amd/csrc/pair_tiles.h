@@ -1,5 +1,6 @@
 // The tile-pair skeleton of the two all-pairs kernels, ibs_pairs_kernel (ibs_kernels.hip, int8 matrix pipe) and
-// grm_pairs_kernel (grm_kernels.hip, fp32 matrix pipe); arithmetic, LDS image, operand lanes and epilogue stay in their files.
+// grm_pairs_kernel (grm_kernels.hip, fp32 matrix pipe; grm_windows_kernel beside it puts a window of sites on grid.y where
+// the site group is); arithmetic, LDS image, operand lanes and epilogue stay in their files.
 // ld_band_kernel (ld_kernels.hip) takes the loader, the lanes and the band's pair map from here; its work split is its own.
 // Work split.  The result [n_rows][n_rows] is symmetric, so only the tile pairs (I, J), J >= I, of PT_T = 128 rows a side are
 // computed: grid.x = the pair index, row I of the upper triangle holding tiles - I pairs.  grid.y = the site groups, group g

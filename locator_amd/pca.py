@@ -40,7 +40,8 @@ angle of eigenvector p by at most 2 ||E||_F / (K_used gap_p) (Davis-Kahan).  Eac
 the same bytes.
 
 Not built: --phased and --dosage inputs; projecting the samples of another file onto kept components; a plot;
-pairwise-complete normalisation instead of mean imputation; an eigen-solver on the device.
+pairwise-complete normalisation instead of mean imputation; an eigen-solver on the device.  The components of single
+windows of the genome and how they differ along it: locator_amd.localpca.
 """
 from __future__ import annotations
 
