@@ -7,7 +7,8 @@ include/locator_hip_pca.h (the pca command): PCA_PROTOTYPES and its LOC_PCA_* co
 include/locator_hip_ld.h (the ld command): LD_PROTOTYPES and its LOC_LD_* constants, and
 include/locator_hip_spa.h (the spa command): SPA_PROTOTYPES and its LOC_SPA_* constants, and
 include/locator_hip_admix.h (the admix command): ADMIX_PROTOTYPES and its LOC_ADMIX_* constants, and
-include/locator_hip_localpca.h (the localpca command): LOCALPCA_PROTOTYPES and its LOC_LOCALPCA_* constants.  No torch here: locator_amd.genotypes and the command line import this module before torch.
+include/locator_hip_localpca.h (the localpca command): LOCALPCA_PROTOTYPES and its LOC_LOCALPCA_* constants, and
+include/locator_hip_paint.h (the paint command): PAINT_PROTOTYPES and its LOC_PAINT_* constants.  No torch here: locator_amd.genotypes and the command line import this module before torch.
 
 The reader knows the header's spelling, not C: one declaration per `;`, scalar types from _SCALARS, comments only as
 /* */.  Anything else raises with the offending text, so that a header edit cannot silently drop or mis-type an entry."""
@@ -33,6 +34,8 @@ SPA_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_spa.h")
 ADMIX_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_admix.h")
 # the localpca command's entry point (locator_amd/localpca.py): functions and LOC_LOCALPCA_* integer constants only
 LOCALPCA_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_localpca.h")
+# the paint command's entry points (locator_amd/paint.py): functions and LOC_PAINT_* integer constants only
+PAINT_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_paint.h")
 
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
             "float": C.c_float, "double": C.c_double}
@@ -181,3 +184,13 @@ if (_structs or set(LOCALPCA_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES
         or not all(k.startswith("LOC_LOCALPCA_") and isinstance(v, int) for k, v in LOCALPCA_CONSTANTS.items())):
     raise ValueError(f"{LOCALPCA_HEADER} may declare new functions and LOC_LOCALPCA_* integer constants only")
 globals().update(LOCALPCA_CONSTANTS)
+if not os.path.exists(PAINT_HEADER):
+    raise FileNotFoundError(f"{PAINT_HEADER} not found: it declares the entry points of the paint command")
+with open(PAINT_HEADER) as _f:
+    PAINT_CONSTANTS, _structs, PAINT_PROTOTYPES = parse(_f.read())
+if (_structs or set(PAINT_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES) | set(REGION_PROTOTYPES) | set(NEIGHBOR_PROTOTYPES)
+                                         | set(PCA_PROTOTYPES) | set(LD_PROTOTYPES) | set(SPA_PROTOTYPES) | set(ADMIX_PROTOTYPES)
+                                         | set(LOCALPCA_PROTOTYPES))
+        or not all(k.startswith("LOC_PAINT_") and isinstance(v, int) for k, v in PAINT_CONSTANTS.items())):
+    raise ValueError(f"{PAINT_HEADER} may declare new functions and LOC_PAINT_* integer constants only")
+globals().update(PAINT_CONSTANTS)

@@ -32,7 +32,7 @@ def use_library(path):
 # command's: include/locator_hip_regions.h, REGION_SIGNATURES; the neighbors command's: include/locator_hip_neighbors.h,
 # NEIGHBOR_SIGNATURES; the pca command's: include/locator_hip_pca.h, PCA_SIGNATURES; the ld command's:
 # include/locator_hip_ld.h, LD_SIGNATURES; the spa command's: include/locator_hip_spa.h, SPA_SIGNATURES; the admix command's:
-# include/locator_hip_admix.h, ADMIX_SIGNATURES; the localpca command's: include/locator_hip_localpca.h, LOCALPCA_SIGNATURES) and
+# include/locator_hip_admix.h, ADMIX_SIGNATURES; the localpca command's: include/locator_hip_localpca.h, LOCALPCA_SIGNATURES; the paint command's: include/locator_hip_paint.h, PAINT_SIGNATURES) and
 # nothing here.
 Dims, Layout, Tuning, Net, CbState = (_abi.STRUCTS[n] for n in ("loc_dims", "loc_layout", "loc_tuning", "loc_net",
                                                                 "loc_cb_state"))
@@ -45,6 +45,7 @@ LD_SIGNATURES = _abi.LD_PROTOTYPES
 SPA_SIGNATURES = _abi.SPA_PROTOTYPES
 ADMIX_SIGNATURES = _abi.ADMIX_PROTOTYPES
 LOCALPCA_SIGNATURES = _abi.LOCALPCA_PROTOTYPES
+PAINT_SIGNATURES = _abi.PAINT_PROTOTYPES
 
 
 class LocatorHipError(RuntimeError):
@@ -65,7 +66,8 @@ def load():
             "or `make -C locator_amd/csrc`.  locator_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **REGION_SIGNATURES, **NEIGHBOR_SIGNATURES,
-                              **PCA_SIGNATURES, **LD_SIGNATURES, **SPA_SIGNATURES, **ADMIX_SIGNATURES, **LOCALPCA_SIGNATURES}.items():
+                              **PCA_SIGNATURES, **LD_SIGNATURES, **SPA_SIGNATURES, **ADMIX_SIGNATURES, **LOCALPCA_SIGNATURES,
+                              **PAINT_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

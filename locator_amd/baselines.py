@@ -138,12 +138,17 @@ def read_inputs(a, prog):
     return G.read_matrix(a.matrix)
 
 
-def read_inputs_sites(a, prog):
+def read_inputs_sites(a, prog, phase=False):
     """(gt, samples, chrom, pos) for the LD window: read_inputs' answers and the variants' CHROM / POS tables.  A --matrix has
-    one chromosome and no positions (pos None)."""
+    one chromosome and no positions (pos None).  phase (the paint command): the calls must be phased, so a --matrix and an
+    input with a heterozygous call written without phase are refused as locator.py --phased refuses them."""
     from . import genotypes as G
+    if phase and a.zarr is None and a.vcf is None:
+        raise SystemExit(f"{prog} needs --vcf or --zarr: an allele-count --matrix carries no phase")
     if a.zarr is not None:
         callset = G.open_group(a.zarr, mode="r")
+        if phase:
+            refuse_unphased(G.zarr_unphased_hets(callset), f"{a.zarr}: calldata/GT_phased", prog)
         try:
             sites = G.zarr_sites(callset)
         except KeyError as e:
@@ -151,10 +156,18 @@ def read_inputs_sites(a, prog):
         return (np.asarray(callset["calldata/GT"][:], dtype=np.int8), np.asarray(callset["samples"][:]), sites["variants/CHROM"],
                 sites["variants/POS"])
     if a.vcf is not None:
-        vcf = G.read_vcf(a.vcf, sites=True)
+        vcf = G.read_vcf(a.vcf, phase=phase, sites=True)
+        if phase:
+            refuse_unphased(vcf["unphased_hets"], a.vcf, prog)
         return vcf["calldata/GT"], vcf["samples"], vcf["variants/CHROM"], vcf["variants/POS"]
     gt, samples = read_inputs(a, prog)
     return gt, samples, None, None
+
+
+def refuse_unphased(n, where, prog):
+    """The refusal of n heterozygous calls without phase (n None or 0: none is known of)."""
+    if n:
+        raise SystemExit(f"{prog}: {where} has {n} heterozygous call(s) without phase (written 'a/b'); phase them first")
 
 
 def read_locations(sample_data, samples, prog):
@@ -234,12 +247,14 @@ def parse_args(parser, argv):
     return a
 
 
-def prelude(parser, a, launch, sites=False):
+def prelude(parser, a, launch, sites=False, phase=False):
     """Parsed arguments -> (c, P, samples, locs, idx): the count matrix of the sites a fit would train on, its ploidy, the sample
     IDs, their locations (None when the command's --sample_data is optional and was not given), the site indices.  Without --host and without a GPU it refuses (require_gpu) before anything is read.
     With --ld_prune the sites are pruned first (ld.prune_sites: in ascending variant index, on the device unless --host); idx
     keeps its survivors in its own order and a.ld_summary holds the entries the summaries gain.  The site tables are read
-    only then, or with sites=True (localpca), which appends the CHROM and POS of idx to the answer (None, None for a --matrix)."""
+    only then, or with sites=True (localpca), which appends the CHROM and POS of idx to the answer (None, None for a --matrix).
+    phase=True (paint, with sites=True): phased calls are required (read_inputs_sites) and the calls themselves, (variants,
+    samples, 2), are appended after them: the haplotype view needs what the counts have summed."""
     if a.gpu_number is not None:
         for var in ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
             os.environ[var] = a.gpu_number
@@ -251,7 +266,7 @@ def prelude(parser, a, launch, sites=False):
     prune = getattr(a, "ld_prune", None) is not None
     chrom = pos = None
     if prune or sites:
-        gt, samples, chrom, pos = read_inputs_sites(a, parser.prog)
+        gt, samples, chrom, pos = read_inputs_sites(a, parser.prog, phase)
     else:
         gt, samples = read_inputs(a, parser.prog)
     locs = None if a.sample_data is None else read_locations(a.sample_data, samples, parser.prog)
@@ -269,5 +284,6 @@ def prelude(parser, a, launch, sites=False):
         raise SystemExit(f"{parser.prog}: {e}") from None
     if sites:
         at = np.asarray(idx, dtype=np.int64)
-        return c, P, samples, locs, idx, None if chrom is None else np.asarray(chrom)[at], None if pos is None else np.asarray(pos)[at]
+        answer = (c, P, samples, locs, idx, None if chrom is None else np.asarray(chrom)[at], None if pos is None else np.asarray(pos)[at])
+        return answer + (gt,) if phase else answer
     return c, P, samples, locs, idx
