@@ -8,7 +8,8 @@ include/locator_hip_ld.h (the ld command): LD_PROTOTYPES and its LOC_LD_* consta
 include/locator_hip_spa.h (the spa command): SPA_PROTOTYPES and its LOC_SPA_* constants, and
 include/locator_hip_admix.h (the admix command): ADMIX_PROTOTYPES and its LOC_ADMIX_* constants, and
 include/locator_hip_localpca.h (the localpca command): LOCALPCA_PROTOTYPES and its LOC_LOCALPCA_* constants, and
-include/locator_hip_paint.h (the paint command): PAINT_PROTOTYPES and its LOC_PAINT_* constants.  No torch here: locator_amd.genotypes and the command line import this module before torch.
+include/locator_hip_paint.h (the paint command): PAINT_PROTOTYPES and its LOC_PAINT_* constants, and
+include/locator_hip_ibd.h (the ibd command): IBD_PROTOTYPES and its LOC_IBD_* constants.  No torch here: locator_amd.genotypes and the command line import this module before torch.
 
 The reader knows the header's spelling, not C: one declaration per `;`, scalar types from _SCALARS, comments only as
 /* */.  Anything else raises with the offending text, so that a header edit cannot silently drop or mis-type an entry."""
@@ -36,6 +37,8 @@ ADMIX_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_admix.h")
 LOCALPCA_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_localpca.h")
 # the paint command's entry points (locator_amd/paint.py): functions and LOC_PAINT_* integer constants only
 PAINT_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_paint.h")
+# the ibd command's entry points (locator_amd/ibd.py): functions and LOC_IBD_* integer constants only
+IBD_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_ibd.h")
 
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
             "float": C.c_float, "double": C.c_double}
@@ -194,3 +197,13 @@ if (_structs or set(PAINT_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES) |
         or not all(k.startswith("LOC_PAINT_") and isinstance(v, int) for k, v in PAINT_CONSTANTS.items())):
     raise ValueError(f"{PAINT_HEADER} may declare new functions and LOC_PAINT_* integer constants only")
 globals().update(PAINT_CONSTANTS)
+if not os.path.exists(IBD_HEADER):
+    raise FileNotFoundError(f"{IBD_HEADER} not found: it declares the entry points of the ibd command")
+with open(IBD_HEADER) as _f:
+    IBD_CONSTANTS, _structs, IBD_PROTOTYPES = parse(_f.read())
+if (_structs or set(IBD_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES) | set(REGION_PROTOTYPES) | set(NEIGHBOR_PROTOTYPES)
+                                       | set(PCA_PROTOTYPES) | set(LD_PROTOTYPES) | set(SPA_PROTOTYPES) | set(ADMIX_PROTOTYPES)
+                                       | set(LOCALPCA_PROTOTYPES) | set(PAINT_PROTOTYPES))
+        or not all(k.startswith("LOC_IBD_") and isinstance(v, int) for k, v in IBD_CONSTANTS.items())):
+    raise ValueError(f"{IBD_HEADER} may declare new functions and LOC_IBD_* integer constants only")
+globals().update(IBD_CONSTANTS)

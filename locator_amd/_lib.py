@@ -32,7 +32,8 @@ def use_library(path):
 # command's: include/locator_hip_regions.h, REGION_SIGNATURES; the neighbors command's: include/locator_hip_neighbors.h,
 # NEIGHBOR_SIGNATURES; the pca command's: include/locator_hip_pca.h, PCA_SIGNATURES; the ld command's:
 # include/locator_hip_ld.h, LD_SIGNATURES; the spa command's: include/locator_hip_spa.h, SPA_SIGNATURES; the admix command's:
-# include/locator_hip_admix.h, ADMIX_SIGNATURES; the localpca command's: include/locator_hip_localpca.h, LOCALPCA_SIGNATURES; the paint command's: include/locator_hip_paint.h, PAINT_SIGNATURES) and
+# include/locator_hip_admix.h, ADMIX_SIGNATURES; the localpca command's: include/locator_hip_localpca.h, LOCALPCA_SIGNATURES; the paint command's: include/locator_hip_paint.h, PAINT_SIGNATURES;
+# the ibd command's: include/locator_hip_ibd.h, IBD_SIGNATURES) and
 # nothing here.
 Dims, Layout, Tuning, Net, CbState = (_abi.STRUCTS[n] for n in ("loc_dims", "loc_layout", "loc_tuning", "loc_net",
                                                                 "loc_cb_state"))
@@ -46,6 +47,7 @@ SPA_SIGNATURES = _abi.SPA_PROTOTYPES
 ADMIX_SIGNATURES = _abi.ADMIX_PROTOTYPES
 LOCALPCA_SIGNATURES = _abi.LOCALPCA_PROTOTYPES
 PAINT_SIGNATURES = _abi.PAINT_PROTOTYPES
+IBD_SIGNATURES = _abi.IBD_PROTOTYPES
 
 
 class LocatorHipError(RuntimeError):
@@ -67,7 +69,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **REGION_SIGNATURES, **NEIGHBOR_SIGNATURES,
                               **PCA_SIGNATURES, **LD_SIGNATURES, **SPA_SIGNATURES, **ADMIX_SIGNATURES, **LOCALPCA_SIGNATURES,
-                              **PAINT_SIGNATURES}.items():
+                              **PAINT_SIGNATURES, **IBD_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -1,6 +1,7 @@
 """What the baseline commands (neighbors.py: IBS distances and a kNN placement; pca.py: principal components and a PC-regression
-placement) share: the count matrix, the inputs, the common command line, the errors of a placement, the choice of the smallest
-leave-one-out median and the common part of the summaries.  Messages name the command that runs (`prog`: "locator_amd.pca")."""
+placement; paint.py and ibd.py: a top-k placement from a sample-by-sample weight) share: the count matrix, the inputs, the
+common command line, the errors of a placement, the choice of the smallest leave-one-out median, the top-k weighted placement
+and the common part of the summaries.  Messages name the command that runs (`prog`: "locator_amd.pca")."""
 import argparse
 import io
 import os
@@ -81,6 +82,28 @@ def choose_smallest_median(placed, locs, located, longlat, nothing):
     if np.isnan(med).all():
         raise ValueError(nothing)
     return int(np.nanargmin(med)) + 1, med
+
+
+def top_donors(W, candidate, kmax):
+    """(nbr int32 [N][kmax], weight float64 [N][kmax]): for sample s the candidate samples t with W[s][t] > 0 by W descending,
+    ties to the lower index; -1 and 0 past their number."""
+    N = W.shape[0]
+    nbr, weight = np.full((N, kmax), -1, dtype=np.int32), np.zeros((N, kmax))
+    cand = np.flatnonzero(candidate)
+    for s in range(N):
+        ts = cand[W[s, cand] > 0]
+        ts = ts[np.argsort(-W[s, ts], kind="stable")][:kmax]
+        nbr[s, :len(ts)], weight[s, :len(ts)] = ts, W[s, ts]
+    return nbr, weight
+
+
+def placements(nbr, weight, locs):
+    """[kmax][N][2]: for k = 1 .. kmax the weighted mean location of each sample's first k donors, summed in rank order; a
+    sample with fewer than k donors keeps the mean over those it has, one with none is NaN."""
+    xy = np.where((nbr >= 0)[:, :, None], np.asarray(locs, dtype=np.float64)[np.maximum(nbr, 0)], 0.0) * weight[:, :, None]
+    sums, tot = np.cumsum(xy, axis=1), np.cumsum(weight, axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.transpose(sums / tot[:, :, None], (1, 0, 2))
 
 
 def r2(a, b):

@@ -289,26 +289,8 @@ def sample_weights(copy, hap, donor_samples, rho, theta, max_haps=MAX_HAPS, reci
     return W, C, ll, nd, len(groups)
 
 
-def top_donors(W, candidate, kmax):
-    """(nbr int32 [N][kmax], weight float64 [N][kmax]): for sample s the candidate samples t with W[s][t] > 0 by W descending,
-    ties to the lower index; -1 and 0 past their number."""
-    N = W.shape[0]
-    nbr, weight = np.full((N, kmax), -1, dtype=np.int32), np.zeros((N, kmax))
-    cand = np.flatnonzero(candidate)
-    for s in range(N):
-        ts = cand[W[s, cand] > 0]
-        ts = ts[np.argsort(-W[s, ts], kind="stable")][:kmax]
-        nbr[s, :len(ts)], weight[s, :len(ts)] = ts, W[s, ts]
-    return nbr, weight
-
-
-def placements(nbr, weight, locs):
-    """[kmax][N][2]: for k = 1 .. kmax the weighted mean location of each sample's first k donors, summed in rank order; a
-    sample with fewer than k donors keeps the mean over those it has, one with none is NaN."""
-    xy = np.where((nbr >= 0)[:, :, None], np.asarray(locs, dtype=np.float64)[np.maximum(nbr, 0)], 0.0) * weight[:, :, None]
-    sums, tot = np.cumsum(xy, axis=1), np.cumsum(weight, axis=1)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return np.transpose(sums / tot[:, :, None], (1, 0, 2))
+# the placement from a sample-by-sample weight is shared with the ibd command: baselines.py holds it, these are its names here
+top_donors, placements = B.top_donors, B.placements
 
 
 # ---------------------------------------------------------------- the command's work
