@@ -1,7 +1,7 @@
 /* Entry points of liblocator_hip.so behind `python -m locator_amd.admix` (locator_amd/csrc/admix_kernels.hip): one EM step of
  * the model-based ancestry proportions (FRAPPE's map, the model of STRUCTURE and ADMIXTURE).  The spelling rules of
  * locator_hip.h hold (one declaration per `;`, comments only as this one), and locator_amd/_abi.py derives the ctypes binding
- * from this file with the same reader (ADMIX_PROTOTYPES, and the LOC_ADMIX_* constants).  As in locator_hip.h: device pointers
+ * from this file with the same reader (EXTENSIONS["admix"], and the LOC_ADMIX_* constants).  As in locator_hip.h: device pointers
  * unless named h_*, `stream` a hipStream_t, 0 = success, -1 = bad arguments with loc_last_error set and nothing launched.  The
  * NumPy definition is locator_amd/admix.py: step_host. */
 #ifndef LOCATOR_HIP_ADMIX_H

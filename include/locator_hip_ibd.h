@@ -1,7 +1,7 @@
 /* Entry points of liblocator_hip.so behind `python -m locator_amd.ibd` (locator_amd/csrc/ibd_kernels.hip): identity-by-descent
  * segments between phased haplotypes, found on bit planes by integer code alone.  The spelling rules of locator_hip.h hold (one
  * declaration per `;`, comments only as this one), and locator_amd/_abi.py derives the ctypes binding from this file with the
- * same reader (IBD_PROTOTYPES, and the LOC_IBD_* constants).  As in locator_hip.h: device pointers unless named h_*, `stream` a
+ * same reader (EXTENSIONS["ibd"], and the LOC_IBD_* constants).  As in locator_hip.h: device pointers unless named h_*, `stream` a
  * hipStream_t, 0 = success, -1 = bad arguments with loc_last_error set and nothing launched.  The NumPy definitions are
  * locator_amd/ibd.py: pack_host and segments_host; the device gives their answers bit for bit. */
 #ifndef LOCATOR_HIP_IBD_H

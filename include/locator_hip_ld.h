@@ -1,7 +1,7 @@
 /* Entry point of liblocator_hip.so behind `python -m locator_amd.ld` and the --ld_prune option of the neighbors and pca commands
  * (locator_amd/csrc/ld_kernels.hip): the squared correlation r^2 of every site with the sites that follow it inside a window, on
  * the int8 matrix pipe.  The spelling rules of locator_hip.h hold (one declaration per `;`, comments only as this one), and
- * locator_amd/_abi.py derives the ctypes binding from this file with the same reader (LD_PROTOTYPES, and the LOC_LD_*
+ * locator_amd/_abi.py derives the ctypes binding from this file with the same reader (EXTENSIONS["ld"], and the LOC_LD_*
  * constants).  As in locator_hip.h: device pointers unless named h_*, `stream` a hipStream_t, 0 = success, -1 = bad arguments
  * with loc_last_error set and nothing launched. */
 #ifndef LOCATOR_HIP_LD_H

@@ -1,7 +1,7 @@
 /* Entry point of liblocator_hip.so behind `python -m locator_amd.localpca` (locator_amd/csrc/grm_kernels.hip): one relationship
  * matrix G_w = Z_w Z_w' per window of sites, all windows in one launch on the fp32 matrix pipe.  The spelling rules of
  * locator_hip.h hold (one declaration per `;`, comments only as this one), and locator_amd/_abi.py derives the ctypes binding
- * from this file with the same reader (LOCALPCA_PROTOTYPES, and the LOC_LOCALPCA_* constants).  As in locator_hip.h: device
+ * from this file with the same reader (EXTENSIONS["localpca"], and the LOC_LOCALPCA_* constants).  As in locator_hip.h: device
  * pointers unless named h_*, `stream` a hipStream_t, 0 = success, -1 = bad arguments with loc_last_error set and nothing
  * launched.  The NumPy definition is locator_amd/localpca.py: windows_host. */
 #ifndef LOCATOR_HIP_LOCALPCA_H

@@ -1,7 +1,7 @@
 /* Entry points of liblocator_hip.so behind `python -m locator_amd.neighbors` (locator_amd/csrc/ibs_kernels.hip): the pairwise
  * identity-by-state statistics of all sample pairs over all sites on the int8 matrix pipe, and each row's nearest candidates.
  * The spelling rules of locator_hip.h hold (one declaration per `;`, comments only as this one), and locator_amd/_abi.py
- * derives the ctypes binding from this file with the same reader (NEIGHBOR_PROTOTYPES, and the LOC_IBS_* constants).  As in
+ * derives the ctypes binding from this file with the same reader (EXTENSIONS["neighbor"], and the LOC_IBS_* constants).  As in
  * locator_hip.h: device pointers unless named h_*, `stream` a hipStream_t, 0 = success, -1 = bad arguments with
  * loc_last_error set and nothing launched. */
 #ifndef LOCATOR_HIP_NEIGHBORS_H

@@ -1,7 +1,7 @@
 /* Entry points of liblocator_hip.so behind `python -m locator_amd.paint` (locator_amd/csrc/paint_kernels.hip): the haplotype
  * copying model of Li & Stephens, one normalised forward-backward recursion a recipient haplotype.  The spelling rules of
  * locator_hip.h hold (one declaration per `;`, comments only as this one), and locator_amd/_abi.py derives the ctypes binding
- * from this file with the same reader (PAINT_PROTOTYPES, and the LOC_PAINT_* constants).  As in locator_hip.h: device pointers
+ * from this file with the same reader (EXTENSIONS["paint"], and the LOC_PAINT_* constants).  As in locator_hip.h: device pointers
  * unless named h_*, `stream` a hipStream_t, 0 = success, -1 = bad arguments with loc_last_error set and nothing launched.  The
  * NumPy definition is locator_amd/paint.py: copy_host. */
 #ifndef LOCATOR_HIP_PAINT_H

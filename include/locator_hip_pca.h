@@ -1,7 +1,7 @@
 /* Entry points of liblocator_hip.so behind `python -m locator_amd.pca` (locator_amd/csrc/grm_kernels.hip): the genetic
  * relationship matrix G = Z Z' of all sample pairs over all sites on the fp32 matrix pipe, and the site loadings Z' U of kept
  * eigenvectors.  The spelling rules of locator_hip.h hold (one declaration per `;`, comments only as this one), and
- * locator_amd/_abi.py derives the ctypes binding from this file with the same reader (PCA_PROTOTYPES, and the LOC_PCA_*
+ * locator_amd/_abi.py derives the ctypes binding from this file with the same reader (EXTENSIONS["pca"], and the LOC_PCA_*
  * constants).  As in locator_hip.h: device pointers unless named h_*, `stream` a hipStream_t, 0 = success, -1 = bad arguments
  * with loc_last_error set and nothing launched. */
 #ifndef LOCATOR_HIP_PCA_H

@@ -1,7 +1,7 @@
 /* Entry points of liblocator_hip.so added after version 1 of the C ABI.  include/locator_hip.h is that version, and
  * tests/test_abi.py pins its list of prototypes; a later entry point is declared here, in the same spelling (one declaration
  * per `;`, comments only as this one), and locator_amd/_abi.py derives its ctypes binding from this file in the same way
- * (EXT_PROTOTYPES).  The rules of locator_hip.h hold: device pointers unless named h_*, `stream` a hipStream_t, 0 = success,
+ * (EXTENSIONS["ext"]).  The rules of locator_hip.h hold: device pointers unless named h_*, `stream` a hipStream_t, 0 = success,
  * -1 = bad arguments with loc_last_error set and nothing launched. */
 #ifndef LOCATOR_HIP_QUERY_H
 #define LOCATOR_HIP_QUERY_H

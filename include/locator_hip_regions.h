@@ -1,7 +1,7 @@
 /* Entry points of liblocator_hip.so behind `python -m locator_amd.regions` (locator_amd/csrc/region_kernels.hip): which map
  * region holds each predicted point, and the nearest outline vertex of a point that no region holds.  The spelling rules of
  * locator_hip.h hold (one declaration per `;`, comments only as this one), and locator_amd/_abi.py derives the ctypes binding
- * from this file with the same reader (REGION_PROTOTYPES, and the LOC_REGION_* constants).  As in locator_hip.h: device
+ * from this file with the same reader (EXTENSIONS["region"], and the LOC_REGION_* constants).  As in locator_hip.h: device
  * pointers unless named h_*, `stream` a hipStream_t, 0 = success, -1 = bad arguments with loc_last_error set and nothing
  * launched. */
 #ifndef LOCATOR_HIP_REGIONS_H

@@ -1,7 +1,7 @@
 /* Entry points of liblocator_hip.so behind `python -m locator_amd.spa` (locator_amd/csrc/spa_kernels.hip): logistic
  * allele-frequency surfaces fitted per site, and the genotype log-likelihood of every sample at every node of a grid.  The
  * spelling rules of locator_hip.h hold (one declaration per `;`, comments only as this one), and locator_amd/_abi.py derives the
- * ctypes binding from this file with the same reader (SPA_PROTOTYPES, and the LOC_SPA_* constants).  As in locator_hip.h: device
+ * ctypes binding from this file with the same reader (EXTENSIONS["spa"], and the LOC_SPA_* constants).  As in locator_hip.h: device
  * pointers unless named h_*, `stream` a hipStream_t, 0 = success, -1 = bad arguments with loc_last_error set and nothing
  * launched.  The NumPy definitions are locator_amd/spa.py: fit_host and grid_host. */
 #ifndef LOCATOR_HIP_SPA_H

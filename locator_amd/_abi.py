@@ -1,44 +1,32 @@
 """The C ABI as include/locator_hip.h declares it, read once at import: the LOC_* constants as module attributes, the
 structs as ctypes Structures (STRUCTS) and the prototypes as (restype, argtypes) pairs (PROTOTYPES).  Nothing else in the
-package restates the header.  include/locator_hip_query.h (later entry points) is read likewise: EXT_PROTOTYPES, and so is
-include/locator_hip_regions.h (the regions command): REGION_PROTOTYPES and its LOC_REGION_* constants, and
-include/locator_hip_neighbors.h (the neighbors command): NEIGHBOR_PROTOTYPES and its LOC_IBS_* constants, and
-include/locator_hip_pca.h (the pca command): PCA_PROTOTYPES and its LOC_PCA_* constants, and
-include/locator_hip_ld.h (the ld command): LD_PROTOTYPES and its LOC_LD_* constants, and
-include/locator_hip_spa.h (the spa command): SPA_PROTOTYPES and its LOC_SPA_* constants, and
-include/locator_hip_admix.h (the admix command): ADMIX_PROTOTYPES and its LOC_ADMIX_* constants, and
-include/locator_hip_localpca.h (the localpca command): LOCALPCA_PROTOTYPES and its LOC_LOCALPCA_* constants, and
-include/locator_hip_paint.h (the paint command): PAINT_PROTOTYPES and its LOC_PAINT_* constants, and
-include/locator_hip_ibd.h (the ibd command): IBD_PROTOTYPES and its LOC_IBD_* constants.  No torch here: locator_amd.genotypes and the command line import this module before torch.
+package restates the header.  The headers of the later entry points (_EXTENSION_TABLE: one line a header) are read likewise:
+EXTENSIONS[tag] holds a header's path, constants and prototypes, the constants are module attributes too, and ALL_PROTOTYPES
+is what the library binds.  No torch here: locator_amd.genotypes and the command line import this module before torch.
 
 The reader knows the header's spelling, not C: one declaration per `;`, scalar types from _SCALARS, comments only as
 /* */.  Anything else raises with the offending text, so that a header edit cannot silently drop or mis-type an entry."""
 import ctypes as C
 import os
 import re
+from typing import NamedTuple
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "locator_hip.h")
-# entry points added after version 1 of the ABI (the prototype list of locator_hip.h, which tests/test_abi.py pins): the same
-# spelling, read by the same parser into EXT_PROTOTYPES; it declares functions only
-EXT_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_query.h")
-# the regions command's entry points (locator_amd/regions.py): functions and LOC_REGION_* integer constants only
-REGION_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_regions.h")
-# the neighbors command's entry points (locator_amd/neighbors.py): functions and LOC_IBS_* integer constants only
-NEIGHBOR_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_neighbors.h")
-# the pca command's entry points (locator_amd/pca.py): functions and LOC_PCA_* integer constants only
-PCA_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_pca.h")
-# the ld command's entry point (locator_amd/ld.py): functions and LOC_LD_* integer constants only
-LD_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_ld.h")
-# the spa command's entry points (locator_amd/spa.py): functions and LOC_SPA_* integer constants only
-SPA_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_spa.h")
-# the admix command's entry points (locator_amd/admix.py): functions and LOC_ADMIX_* integer constants only
-ADMIX_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_admix.h")
-# the localpca command's entry point (locator_amd/localpca.py): functions and LOC_LOCALPCA_* integer constants only
-LOCALPCA_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_localpca.h")
-# the paint command's entry points (locator_amd/paint.py): functions and LOC_PAINT_* integer constants only
-PAINT_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_paint.h")
-# the ibd command's entry points (locator_amd/ibd.py): functions and LOC_IBD_* integer constants only
-IBD_HEADER = os.path.join(os.path.dirname(HEADER), "locator_hip_ibd.h")
+# The headers of the entry points added after version 1 of the ABI (the prototype list of locator_hip.h, which tests/test_abi.py
+# pins), in the same spelling: (tag, file, the prefix its integer constants carry; None: it declares functions only).  A header
+# declares no struct, and no function or constant that another header declares.
+_EXTENSION_TABLE = (
+    ("ext", "locator_hip_query.h", None),
+    ("region", "locator_hip_regions.h", "LOC_REGION_"),
+    ("neighbor", "locator_hip_neighbors.h", "LOC_IBS_"),
+    ("pca", "locator_hip_pca.h", "LOC_PCA_"),
+    ("ld", "locator_hip_ld.h", "LOC_LD_"),
+    ("spa", "locator_hip_spa.h", "LOC_SPA_"),
+    ("admix", "locator_hip_admix.h", "LOC_ADMIX_"),
+    ("localpca", "locator_hip_localpca.h", "LOC_LOCALPCA_"),
+    ("paint", "locator_hip_paint.h", "LOC_PAINT_"),
+    ("ibd", "locator_hip_ibd.h", "LOC_IBD_"),
+)
 
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
             "float": C.c_float, "double": C.c_double}
@@ -121,89 +109,27 @@ if not os.path.exists(HEADER):
 with open(HEADER) as _f:
     CONSTANTS, STRUCTS, PROTOTYPES = parse(_f.read())
 globals().update(CONSTANTS)
-if not os.path.exists(EXT_HEADER):
-    raise FileNotFoundError(f"{EXT_HEADER} not found: it declares the entry points added after include/locator_hip.h")
-with open(EXT_HEADER) as _f:
-    _consts, _structs, EXT_PROTOTYPES = parse(_f.read())
-if _consts or _structs or set(EXT_PROTOTYPES) & set(PROTOTYPES):
-    raise ValueError(f"{EXT_HEADER} may declare new functions only")
-if not os.path.exists(REGION_HEADER):
-    raise FileNotFoundError(f"{REGION_HEADER} not found: it declares the entry points of the regions command")
-with open(REGION_HEADER) as _f:
-    REGION_CONSTANTS, _structs, REGION_PROTOTYPES = parse(_f.read())
-if (_structs or set(REGION_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES)) or set(REGION_CONSTANTS) & set(CONSTANTS)
-        or not all(k.startswith("LOC_REGION_") and isinstance(v, int) for k, v in REGION_CONSTANTS.items())):
-    raise ValueError(f"{REGION_HEADER} may declare new functions and LOC_REGION_* integer constants only")
-globals().update(REGION_CONSTANTS)
-if not os.path.exists(NEIGHBOR_HEADER):
-    raise FileNotFoundError(f"{NEIGHBOR_HEADER} not found: it declares the entry points of the neighbors command")
-with open(NEIGHBOR_HEADER) as _f:
-    NEIGHBOR_CONSTANTS, _structs, NEIGHBOR_PROTOTYPES = parse(_f.read())
-if (_structs or set(NEIGHBOR_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES) | set(REGION_PROTOTYPES))
-        or not all(k.startswith("LOC_IBS_") and isinstance(v, int) for k, v in NEIGHBOR_CONSTANTS.items())):
-    raise ValueError(f"{NEIGHBOR_HEADER} may declare new functions and LOC_IBS_* integer constants only")
-globals().update(NEIGHBOR_CONSTANTS)
-if not os.path.exists(PCA_HEADER):
-    raise FileNotFoundError(f"{PCA_HEADER} not found: it declares the entry points of the pca command")
-with open(PCA_HEADER) as _f:
-    PCA_CONSTANTS, _structs, PCA_PROTOTYPES = parse(_f.read())
-if (_structs or set(PCA_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES) | set(REGION_PROTOTYPES) | set(NEIGHBOR_PROTOTYPES))
-        or not all(k.startswith("LOC_PCA_") and isinstance(v, int) for k, v in PCA_CONSTANTS.items())):
-    raise ValueError(f"{PCA_HEADER} may declare new functions and LOC_PCA_* integer constants only")
-globals().update(PCA_CONSTANTS)
-if not os.path.exists(LD_HEADER):
-    raise FileNotFoundError(f"{LD_HEADER} not found: it declares the entry point of the ld command")
-with open(LD_HEADER) as _f:
-    LD_CONSTANTS, _structs, LD_PROTOTYPES = parse(_f.read())
-if (_structs or set(LD_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES) | set(REGION_PROTOTYPES) | set(NEIGHBOR_PROTOTYPES)
-                                      | set(PCA_PROTOTYPES))
-        or not all(k.startswith("LOC_LD_") and isinstance(v, int) for k, v in LD_CONSTANTS.items())):
-    raise ValueError(f"{LD_HEADER} may declare new functions and LOC_LD_* integer constants only")
-globals().update(LD_CONSTANTS)
-if not os.path.exists(SPA_HEADER):
-    raise FileNotFoundError(f"{SPA_HEADER} not found: it declares the entry points of the spa command")
-with open(SPA_HEADER) as _f:
-    SPA_CONSTANTS, _structs, SPA_PROTOTYPES = parse(_f.read())
-if (_structs or set(SPA_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES) | set(REGION_PROTOTYPES) | set(NEIGHBOR_PROTOTYPES)
-                                       | set(PCA_PROTOTYPES) | set(LD_PROTOTYPES))
-        or not all(k.startswith("LOC_SPA_") and isinstance(v, int) for k, v in SPA_CONSTANTS.items())):
-    raise ValueError(f"{SPA_HEADER} may declare new functions and LOC_SPA_* integer constants only")
-globals().update(SPA_CONSTANTS)
-if not os.path.exists(ADMIX_HEADER):
-    raise FileNotFoundError(f"{ADMIX_HEADER} not found: it declares the entry points of the admix command")
-with open(ADMIX_HEADER) as _f:
-    ADMIX_CONSTANTS, _structs, ADMIX_PROTOTYPES = parse(_f.read())
-if (_structs or set(ADMIX_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES) | set(REGION_PROTOTYPES) | set(NEIGHBOR_PROTOTYPES)
-                                         | set(PCA_PROTOTYPES) | set(LD_PROTOTYPES) | set(SPA_PROTOTYPES))
-        or not all(k.startswith("LOC_ADMIX_") and isinstance(v, int) for k, v in ADMIX_CONSTANTS.items())):
-    raise ValueError(f"{ADMIX_HEADER} may declare new functions and LOC_ADMIX_* integer constants only")
-globals().update(ADMIX_CONSTANTS)
-if not os.path.exists(LOCALPCA_HEADER):
-    raise FileNotFoundError(f"{LOCALPCA_HEADER} not found: it declares the entry point of the localpca command")
-with open(LOCALPCA_HEADER) as _f:
-    LOCALPCA_CONSTANTS, _structs, LOCALPCA_PROTOTYPES = parse(_f.read())
-if (_structs or set(LOCALPCA_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES) | set(REGION_PROTOTYPES) | set(NEIGHBOR_PROTOTYPES)
-                                            | set(PCA_PROTOTYPES) | set(LD_PROTOTYPES) | set(SPA_PROTOTYPES) | set(ADMIX_PROTOTYPES))
-        or not all(k.startswith("LOC_LOCALPCA_") and isinstance(v, int) for k, v in LOCALPCA_CONSTANTS.items())):
-    raise ValueError(f"{LOCALPCA_HEADER} may declare new functions and LOC_LOCALPCA_* integer constants only")
-globals().update(LOCALPCA_CONSTANTS)
-if not os.path.exists(PAINT_HEADER):
-    raise FileNotFoundError(f"{PAINT_HEADER} not found: it declares the entry points of the paint command")
-with open(PAINT_HEADER) as _f:
-    PAINT_CONSTANTS, _structs, PAINT_PROTOTYPES = parse(_f.read())
-if (_structs or set(PAINT_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES) | set(REGION_PROTOTYPES) | set(NEIGHBOR_PROTOTYPES)
-                                         | set(PCA_PROTOTYPES) | set(LD_PROTOTYPES) | set(SPA_PROTOTYPES) | set(ADMIX_PROTOTYPES)
-                                         | set(LOCALPCA_PROTOTYPES))
-        or not all(k.startswith("LOC_PAINT_") and isinstance(v, int) for k, v in PAINT_CONSTANTS.items())):
-    raise ValueError(f"{PAINT_HEADER} may declare new functions and LOC_PAINT_* integer constants only")
-globals().update(PAINT_CONSTANTS)
-if not os.path.exists(IBD_HEADER):
-    raise FileNotFoundError(f"{IBD_HEADER} not found: it declares the entry points of the ibd command")
-with open(IBD_HEADER) as _f:
-    IBD_CONSTANTS, _structs, IBD_PROTOTYPES = parse(_f.read())
-if (_structs or set(IBD_PROTOTYPES) & (set(PROTOTYPES) | set(EXT_PROTOTYPES) | set(REGION_PROTOTYPES) | set(NEIGHBOR_PROTOTYPES)
-                                       | set(PCA_PROTOTYPES) | set(LD_PROTOTYPES) | set(SPA_PROTOTYPES) | set(ADMIX_PROTOTYPES)
-                                       | set(LOCALPCA_PROTOTYPES) | set(PAINT_PROTOTYPES))
-        or not all(k.startswith("LOC_IBD_") and isinstance(v, int) for k, v in IBD_CONSTANTS.items())):
-    raise ValueError(f"{IBD_HEADER} may declare new functions and LOC_IBD_* integer constants only")
-globals().update(IBD_CONSTANTS)
+
+
+class Extension(NamedTuple):
+    header: str
+    constants: dict
+    prototypes: dict
+
+
+EXTENSIONS = {}
+ALL_PROTOTYPES = dict(PROTOTYPES)
+_declared = set(CONSTANTS) | set(PROTOTYPES)         # by the main header and the table's lines so far
+for _tag, _name, _prefix in _EXTENSION_TABLE:
+    _path = os.path.join(os.path.dirname(HEADER), _name)
+    if not os.path.exists(_path):
+        raise FileNotFoundError(f"{_path} not found: it declares entry points added after include/locator_hip.h")
+    with open(_path) as _f:
+        _consts, _structs, _protos = parse(_f.read())
+    if (_structs or _declared & (set(_consts) | set(_protos))
+            or not all(_prefix is not None and k.startswith(_prefix) and isinstance(v, int) for k, v in _consts.items())):
+        raise ValueError(f"{_path} may declare new functions " + ("only" if _prefix is None else f"and {_prefix}* integer constants only"))
+    _declared |= set(_consts) | set(_protos)
+    EXTENSIONS[_tag] = Extension(_path, _consts, _protos)
+    ALL_PROTOTYPES.update(_protos)
+    globals().update(_consts)

@@ -27,27 +27,11 @@ def use_library(path):
     LIB_PATH = path
 
 
-# The structs and every entry point's (restype, argtypes) come from include/locator_hip.h (locator_amd/_abi.py): a new entry
-# point needs its prototype there (since version 1 of the ABI: in include/locator_hip_query.h, EXT_SIGNATURES; the regions
-# command's: include/locator_hip_regions.h, REGION_SIGNATURES; the neighbors command's: include/locator_hip_neighbors.h,
-# NEIGHBOR_SIGNATURES; the pca command's: include/locator_hip_pca.h, PCA_SIGNATURES; the ld command's:
-# include/locator_hip_ld.h, LD_SIGNATURES; the spa command's: include/locator_hip_spa.h, SPA_SIGNATURES; the admix command's:
-# include/locator_hip_admix.h, ADMIX_SIGNATURES; the localpca command's: include/locator_hip_localpca.h, LOCALPCA_SIGNATURES; the paint command's: include/locator_hip_paint.h, PAINT_SIGNATURES;
-# the ibd command's: include/locator_hip_ibd.h, IBD_SIGNATURES) and
-# nothing here.
+# The structs and every entry point's (restype, argtypes) come from the headers under include/ (locator_amd/_abi.py): a new entry
+# point needs its prototype in a header, a new header needs one line in _abi's table, and nothing here.
 Dims, Layout, Tuning, Net, CbState = (_abi.STRUCTS[n] for n in ("loc_dims", "loc_layout", "loc_tuning", "loc_net",
                                                                 "loc_cb_state"))
 SIGNATURES = _abi.PROTOTYPES
-EXT_SIGNATURES = _abi.EXT_PROTOTYPES
-REGION_SIGNATURES = _abi.REGION_PROTOTYPES
-NEIGHBOR_SIGNATURES = _abi.NEIGHBOR_PROTOTYPES
-PCA_SIGNATURES = _abi.PCA_PROTOTYPES
-LD_SIGNATURES = _abi.LD_PROTOTYPES
-SPA_SIGNATURES = _abi.SPA_PROTOTYPES
-ADMIX_SIGNATURES = _abi.ADMIX_PROTOTYPES
-LOCALPCA_SIGNATURES = _abi.LOCALPCA_PROTOTYPES
-PAINT_SIGNATURES = _abi.PAINT_PROTOTYPES
-IBD_SIGNATURES = _abi.IBD_PROTOTYPES
 
 
 class LocatorHipError(RuntimeError):
@@ -67,9 +51,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C locator_amd/csrc`.  locator_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **REGION_SIGNATURES, **NEIGHBOR_SIGNATURES,
-                              **PCA_SIGNATURES, **LD_SIGNATURES, **SPA_SIGNATURES, **ADMIX_SIGNATURES, **LOCALPCA_SIGNATURES,
-                              **PAINT_SIGNATURES, **IBD_SIGNATURES}.items():
+    for name, (res, args) in _abi.ALL_PROTOTYPES.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -243,40 +243,33 @@ class _DeviceOps:
 
     def __init__(self, c, P, C, k_groups=0, pitch=None, pad_fill=-1, device="cuda:0", fill=None):
         import torch
-        from . import _lib
-        self.torch, self.lib, self.check = torch, _lib.load(), _lib.check
+        from . import _device as D, _lib
+        self.torch, self.D, self.lib, self.check = torch, D, _lib.load(), _lib.check
         c = np.ascontiguousarray(c, dtype=np.int8)
         self.N, self.K = c.shape
         self.P, self.C, self.k_groups, self.device, self.fill = int(P), int(C), int(k_groups), device, fill
         buf = B.padded(c, pitch, pad_fill)
         self.pitch = int(buf.shape[1])
         with torch.cuda.device(device):
-            self.d_c = torch.from_numpy(buf).to(device)
-            self.work_bytes = int(self.lib.loc_admix_work_bytes(self.N, self.K, self.C, self.k_groups))
-            if self.work_bytes < 0:
-                self.check(-1, "loc_admix_work_bytes")
-            self.work = torch.empty(max(self.work_bytes // 4, 4), dtype=torch.float32, device=device)
+            self.d_c = D.put(buf, np.int8, device)
+            self.work, self.work_bytes = D.work_buffer(self.lib, "loc_admix_work_bytes", self.N, self.K, self.C, self.k_groups,
+                                                       device=device)
             self.d_ll = torch.empty(1, dtype=torch.float64, device=device)
 
     def take(self, Q, F):
-        t = self.torch
-        return (t.from_numpy(np.ascontiguousarray(Q, dtype=np.float32).reshape(self.N, self.C)).to(self.device),
-                t.from_numpy(np.ascontiguousarray(F, dtype=np.float32).reshape(self.K, self.C)).to(self.device))
+        return (self.D.put(np.reshape(Q, (self.N, self.C)), np.float32, self.device),
+                self.D.put(np.reshape(F, (self.K, self.C)), np.float32, self.device))
 
     def step(self, Q, F):
         t = self.torch
         with t.cuda.device(self.device):
             Qn = t.empty((max(self.N, 1), self.C), dtype=t.float32, device=self.device)[:self.N]
             Fn = t.empty((max(self.K, 1), self.C), dtype=t.float32, device=self.device)[:self.K]
-            if self.fill is not None:                                    # tests: what scratch and the outputs hold before
-                bits = int(np.array(self.fill, dtype=np.uint32).view(np.int32))
-                for buf in (self.work, Qn, Fn, self.d_ll):
-                    buf.view(t.int32).fill_(bits)
+            self.D.prefill((self.work, Qn, Fn, self.d_ll), self.fill)    # tests: what scratch and the outputs hold before
             Q, F = Q.contiguous(), F.contiguous()
             self.check(self.lib.loc_admix_step(self.d_c.data_ptr(), self.N, self.K, self.pitch, self.P, self.C, Q.data_ptr(),
                                                F.data_ptr(), Qn.data_ptr(), Fn.data_ptr(), self.d_ll.data_ptr(), self.k_groups,
-                                               self.work.data_ptr(), self.work_bytes, t.cuda.current_stream().cuda_stream),
-                       "loc_admix_step")
+                                               self.work.data_ptr(), self.work_bytes, self.D.stream()), "loc_admix_step")
             return Qn, Fn, float(self.d_ll.item())
 
     def norm(self, dQ, dF):

@@ -1,7 +1,8 @@
 """What the baseline commands (neighbors.py: IBS distances and a kNN placement; pca.py: principal components and a PC-regression
 placement; paint.py and ibd.py: a top-k placement from a sample-by-sample weight) share: the count matrix, the inputs, the
-common command line, the errors of a placement, the choice of the smallest leave-one-out median, the top-k weighted placement
-and the common part of the summaries.  Messages name the command that runs (`prog`: "locator_amd.pca")."""
+common command line (with the --k / --kmax of neighbors, paint and ibd and the haplotype prelude of the latter two), the errors
+of a placement, the choice of the smallest leave-one-out median, the top-k weighted placement with its summary entries and the
+common part of the summaries.  Messages name the command that runs (`prog`: "locator_amd.pca")."""
 import argparse
 import io
 import os
@@ -133,6 +134,56 @@ def placement_summary(c, P, located, xy, locs, longlat, method, how="leave-one-o
     return entries, lines
 
 
+def located_mask(locs, N, prog):
+    """(locs float64 [N][2], located bool [N]) after the refusal of locations none of which is known."""
+    locs = np.asarray(locs, dtype=np.float64).reshape(N, 2)
+    located = ~np.isnan(locs).any(axis=1)
+    if not located.any():
+        raise SystemExit(f"{prog}: no sample of --sample_data has a location: nothing to place from")
+    return locs, located
+
+
+def place_by_weight(prog, W, candidate, kmax, k, c, P, locs, located, longlat, method, nothing):
+    """The placement of the paint and ibd commands from a sample-by-sample weight W [N][N]: (xy [N][2], head entries,
+    placed_own entries, terminal lines, nbr, weight).  nbr, weight: top_donors among the candidates, min(kmax, their number) a
+    sample.  located None (no locations): xy None, no entries and no lines.  Else xy is the W-weighted mean location of the first
+    k donors, k the smallest leave-one-out median error's with "auto" (`nothing` refuses when no k has one); head and lines are
+    placement_summary's for the method word."""
+    kmax = int(min(kmax, np.count_nonzero(candidate)))
+    nbr, weight = top_donors(W, candidate, kmax)
+    if located is None:
+        return None, {}, {}, [], nbr, weight
+    placed = placements(nbr, weight, locs)
+    try:
+        k_auto, med = choose_smallest_median(placed, locs, located, longlat, nothing)
+    except ValueError as e:
+        raise SystemExit(f"{prog}: {e}") from None
+    k_used = min(k_auto if k == "auto" else int(k), kmax)
+    xy = placed[k_used - 1]
+    head, lines = placement_summary(c, P, located, xy, locs, longlat, method)
+    own = {"kmax": kmax, "k": int(k_used), "k_auto": int(k_auto), "k_chosen_by": "auto" if k == "auto" else "--k",
+           "median_error_by_k": [num(v) for v in med]}
+    lines = [f"k = {k_used} ({own['k_chosen_by']}; leave-one-out median error by k, k = 1 .. {kmax}, smallest at k = {k_auto})", *lines]
+    return xy, head, own, lines, nbr, weight
+
+
+def assemble_summary(head, own, placed_own, head_keys, own_keys, placed_keys, host):
+    """The summary of the paint and ibd commands in its key order: the shared head (N, K, P alone without a placement), the
+    command's own entries, those of the placement, and the path."""
+    summary = {**{key: head[key] for key in (head_keys if "n_located" in head else ("N", "K", "P"))},
+               **{key: own[key] for key in own_keys}, **{key: placed_own[key] for key in placed_keys if key in placed_own}}
+    summary["path"] = "host" if host else "device"
+    return summary
+
+
+def write_locs(path, xy, samples):
+    """The x,y,sampleID file of a placement, written as a predlocs file is."""
+    import pandas as pd
+    from ._files import write_atomic
+    frame = pd.DataFrame({"x": xy[:, 0], "y": xy[:, 1], "sampleID": np.asarray(samples).astype(object)})
+    write_atomic(path, lambda fh: frame.to_csv(fh, index=False))
+
+
 def save_npz(fh, **arrays):
     """np.savez_compressed with a fixed member date: two runs that hold the same arrays write the same bytes."""
     with zipfile.ZipFile(fh, "w", zipfile.ZIP_DEFLATED) as z:
@@ -231,6 +282,36 @@ def check_window(parser, a):
         parser.error("--ld_window_bp needs positions: a --matrix has none")
 
 
+KMAX_LIMIT = 64                      # the largest --kmax of the neighbors, paint and ibd commands
+
+
+def add_k_arguments(p, kmax, averaged, listed=None):
+    """--k / --kmax.  kmax: the default; averaged: what k counts ("neighbours"); listed: what the command lists kmax a sample
+    of ("neighbours"), None where it lists none."""
+    p.add_argument("--k", default="auto", help=f"{averaged} averaged: a number, or `auto` (default): the k in 1 .. --kmax with "
+                                               "the smallest leave-one-out median error")
+    p.add_argument("--kmax", default=kmax, type=int, help=("" if listed is None else f"{listed} listed per sample and ") +
+                   f"largest k tried (default {kmax}, at most {KMAX_LIMIT})")
+
+
+def check_k(parser, a):
+    """The parse-time refusals of --k / --kmax; a.k becomes an int unless it is `auto`."""
+    if a.k != "auto":
+        try:
+            a.k = int(a.k)
+        except ValueError:
+            parser.error("--k must be `auto` or a whole number")
+    if not 1 <= a.kmax <= KMAX_LIMIT:
+        parser.error(f"--kmax must be 1 .. {KMAX_LIMIT}")
+    if a.k != "auto" and not 1 <= a.k <= a.kmax:
+        parser.error(f"--k must be `auto` or 1 .. --kmax ({a.kmax})")
+
+
+def check_budget(parser, a):
+    if not a.budget_gb > 0:
+        parser.error("--budget_gb must be positive")
+
+
 def build_parser(prog, description, own, sample_data=True, prune=True, sample_data_help=None):
     """The command line of a baseline: inputs, site filter and output stem, then what own(parser) adds, then the device.
     sample_data False: the command needs no locations, --sample_data is optional (sample_data_help: what it does with them when
@@ -310,3 +391,21 @@ def prelude(parser, a, launch, sites=False, phase=False):
         answer = (c, P, samples, locs, idx, None if chrom is None else np.asarray(chrom)[at], None if pos is None else np.asarray(pos)[at])
         return answer + (gt,) if phase else answer
     return c, P, samples, locs, idx
+
+
+def haplotype_prelude(parser, a, launch, built_for):
+    """Parsed arguments of the paint and ibd commands -> (hap, c, P, samples, locs, chrom, pos): prelude's answers for phased
+    calls with the sites in ascending variant order (a --max_SNPs draw comes in drawn order), hap int8 [sites][2 samples] the
+    site-major haplotype matrix, c the count matrix of the same sites.  built_for: the command's words after "calls of ploidy
+    P: " in the refusal of a ploidy other than 2."""
+    c, P, samples, locs, idx, chrom, pos, gt = prelude(parser, a, launch, sites=True, phase=True)
+    from . import genotypes as G
+    try:
+        if P != 2:
+            raise ValueError(f"calls of ploidy {P}: {built_for}")
+        order = np.argsort(idx, kind="stable")
+        chrom, pos = (None if t is None else np.asarray(t)[order] for t in (chrom, pos))
+        hap, _ = count_matrix_sites(G.haplotypes(np.asarray(gt)), np.asarray(idx)[order])
+    except ValueError as e:
+        raise SystemExit(f"{parser.prog}: {e}") from None
+    return hap, np.ascontiguousarray(c[:, order]), P, samples, locs, chrom, pos

@@ -316,11 +316,7 @@ extern "C" int loc_admix_step(const int8_t* c, int N, int64_t K, int64_t pitch, 
     }
     if (N > 0 && K > 0 && !pt_rows_aligned("loc_admix_step", c, pitch)) return -1;
     const ad_layout L = ad_work(N, K, C, k_groups);
-    if (L.bytes > 0 && (!work || work_bytes < L.bytes || (uintptr_t)work % 16 != 0)) {
-        loc_set_error("loc_admix_step: work of %lld bytes at %p: needs %lld bytes, 16-byte aligned (loc_admix_work_bytes)",
-                      (long long)work_bytes, work, (long long)L.bytes);
-        return -1;
-    }
+    if (!pt_work_ok("loc_admix_step", "loc_admix_work_bytes", work, work_bytes, L.bytes)) return -1;
     hipStream_t s = (hipStream_t)stream;
     if (N == 0 || K == 0) {                       // no call: no row moves and the likelihood is that of nothing
         hipError_t e = hipMemsetAsync(ll, 0, sizeof(double), s);

@@ -398,11 +398,7 @@ extern "C" int loc_grm_pairs(const int8_t* c, int n_rows, int64_t K, int64_t pit
     const pt_groups split = gr_split(n_rows, K, k_groups);
     const int64_t groups = split.groups, tiles = pt_tiles(n_rows), pairs = pt_pairs(tiles);
     const int64_t need = groups * pairs * (int64_t)(GR_T * GR_T * sizeof(float));
-    if (need > 0 && (!work || work_bytes < need || (uintptr_t)work % 16 != 0)) {
-        loc_set_error("loc_grm_pairs: work of %lld bytes at %p: needs %lld bytes, 16-byte aligned (loc_grm_work_bytes)",
-                      (long long)work_bytes, work, (long long)need);
-        return -1;
-    }
+    if (!pt_work_ok("loc_grm_pairs", "loc_grm_work_bytes", work, work_bytes, need)) return -1;
     if (groups > 0) {
         hipLaunchKernelGGL(grm_pairs_kernel, dim3((unsigned)pairs, (unsigned)groups), dim3(GR_NT), 0, (hipStream_t)stream, c,
                            n_rows, K, pitch, mean, scale, (int)tiles, split.per, (float*)work);

@@ -386,11 +386,7 @@ extern "C" int loc_paint_copy(const int8_t* h, int H, int64_t K, int64_t pitch, 
     }
     if (K > 0 && !pt_rows_aligned("loc_paint_copy", h, pitch)) return -1;
     const pk_layout L = pk_work(H, K, R, block);
-    if (L.bytes > 0 && (!work || work_bytes < L.bytes || (uintptr_t)work % 16 != 0)) {
-        loc_set_error("loc_paint_copy: work of %lld bytes at %p: needs %lld bytes, 16-byte aligned (loc_paint_work_bytes)",
-                      (long long)work_bytes, work, (long long)L.bytes);
-        return -1;
-    }
+    if (!pt_work_ok("loc_paint_copy", "loc_paint_work_bytes", work, work_bytes, L.bytes)) return -1;
     hipStream_t s = (hipStream_t)stream;
     std::vector<int32_t> h_rec((size_t)R);
     hipError_t e = hipMemcpyAsync(h_rec.data(), rec, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost, s);

@@ -112,3 +112,10 @@ inline bool pt_rows_aligned(const char* who, const void* c, int64_t pitch) {
     loc_set_error("%s: pitch=%lld and c must be multiples of 16 bytes (rows are read 16 bytes at a time)", who, (long long)pitch);
     return false;
 }
+// ... and for scratch that is missing, misaligned or smaller than the `need` bytes that the entry point `sizer` asks for
+inline bool pt_work_ok(const char* who, const char* sizer, const void* work, int64_t work_bytes, int64_t need) {
+    if (need <= 0 || (work && work_bytes >= need && (uintptr_t)work % 16 == 0)) return true;
+    loc_set_error("%s: work of %lld bytes at %p: needs %lld bytes, 16-byte aligned (%s)", who, (long long)work_bytes, work,
+                  (long long)need, sizer);
+    return false;
+}

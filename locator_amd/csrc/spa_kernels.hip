@@ -422,11 +422,7 @@ extern "C" int loc_spa_grid(const int8_t* c, int Q, int64_t K, int64_t pitch, in
         loc_set_error("loc_spa_grid: Q=%d G=%d in %lld site groups exceed one launch", Q, G, (long long)split.groups);
         return -1;
     }
-    if (need > 0 && (!work || work_bytes < need || (uintptr_t)work % 16 != 0)) {
-        loc_set_error("loc_spa_grid: work of %lld bytes at %p: needs %lld bytes, 16-byte aligned (loc_spa_grid_work_bytes)",
-                      (long long)work_bytes, work, (long long)need);
-        return -1;
-    }
+    if (!pt_work_ok("loc_spa_grid", "loc_spa_grid_work_bytes", work, work_bytes, need)) return -1;
     if (split.groups > 0) {
         hipLaunchKernelGGL(spa_grid_kernel, dim3((unsigned)tg, (unsigned)tq, (unsigned)split.groups), dim3(SP_NT), 0,
                            (hipStream_t)stream, c, Q, K, pitch, -(float)P, theta, used, gx, gy, G, split.per, (float*)work);

@@ -62,7 +62,6 @@ from ._files import write_atomic
 MAX_HAPS = _abi.LOC_IBD_MAX_HAPS
 MAX_GAP = _abi.LOC_IBD_MAX_GAP
 NO_LIMIT = 1 << 62                   # --gap_length without a limit: no difference of two int64 coordinates the command reads reaches it
-KMAX_LIMIT = 64
 PROG = "locator_amd.ibd"
 LAUNCH = "the scans are loc_ibd_scan launches"
 NOTHING_TO_CHOOSE_BY = "no located sample shares a segment with another located sample: nothing to choose k by"
@@ -209,29 +208,28 @@ def _device_batches(h, owner, first, x, P, p0, R, segments, budget, pitch, wpitc
     """(first row, count, length, longest, seg_a, seg_b) of one batch of rows after the other: one loc_ibd_pack launch, then a
     loc_ibd_scan launch a batch and, where segments are wanted, the prefix sum of its count and a loc_ibd_fill launch."""
     import torch as t
-    from . import _lib
+    from . import _device as D, _lib
     lib = _lib.load()
     K, H = h.shape[0], len(owner)
     buf = B.padded(np.ascontiguousarray(h[:, :H]), pitch, pad_fill)
     wp = (H + 7) // 8 * 8 if wpitch is None else int(wpitch)
     W = (K + 63) // 64
-    pattern = None if fill is None else int(np.array(fill, dtype=np.uint32).view(np.int32))
 
     def fresh(shape, dtype):
         v = t.empty(shape, dtype=dtype, device=device)
-        if pattern is not None and v.numel():
-            v.view(t.int32).fill_(pattern)
+        if v.numel():
+            D.prefill((v,), fill)
         return v
 
     with t.cuda.device(device):
-        stream = lambda: t.cuda.current_stream().cuda_stream
-        d_h = t.from_numpy(buf).to(device)
+        stream = D.stream
+        d_h = D.put(buf, np.int8, device)
         d_bits = fresh((2, max(W, 1), max(wp, 8)), t.int64)
         _lib.check(lib.loc_ibd_pack(d_h.data_ptr(), H, K, int(buf.shape[1]), d_bits.data_ptr(), wp, stream()), "loc_ibd_pack")
         del d_h
-        d_owner = t.from_numpy(owner).to(device)
-        d_first = t.from_numpy(pack_first(first, K).view(np.int64)).to(device)
-        d_x = t.from_numpy(x if K else np.zeros(1, dtype=np.int64)).to(device)
+        d_owner = D.put(owner, np.int32, device)
+        d_first = D.put(pack_first(first, K).view(np.int64), np.int64, device)
+        d_x = D.put(x if K else np.zeros(1, dtype=np.int64), np.int64, device)
         step = max(1, int(budget) // ((PAIR_BYTES_SEGMENTS if segments else PAIR_BYTES) * H))
         for a in range(p0, p0 + R, step):
             n = min(step, p0 + R - a)
@@ -300,7 +298,6 @@ def ibd(hap, c, P, samples, locs, chrom=None, pos=None, out=None, params=Params(
         kmax=16, longlat=False, keep_segments=False, keep_matrix=False, host=False, silence=False, device="cuda:0", budget=4 << 30):
     """The command's work for a site-major haplotype matrix hap [K][2N] (c: the count matrix of the same sites, for the shared
     summary entries): returns the summary dict and writes the output files when `out` is given.  locs None: no locations."""
-    import pandas as pd
     from .paint import site_gaps
     hap = np.ascontiguousarray(hap, dtype=np.int8)
     K, H = hap.shape
@@ -316,14 +313,11 @@ def ibd(hap, c, P, samples, locs, chrom=None, pos=None, out=None, params=Params(
         par = check_params(params)
     except ValueError as e:
         raise SystemExit(f"{PROG}: {e} (--seed_sites, --extend_sites, --gap_sites, --seed_length, --gap_length, --min_length)") from None
-    if k != "auto" and not 1 <= int(k) <= kmax or not 1 <= kmax <= KMAX_LIMIT:
-        raise SystemExit(f"{PROG}: --kmax must be 1 .. {KMAX_LIMIT} and --k `auto` or 1 .. --kmax")
+    if k != "auto" and not 1 <= int(k) <= kmax or not 1 <= kmax <= B.KMAX_LIMIT:
+        raise SystemExit(f"{PROG}: --kmax must be 1 .. {B.KMAX_LIMIT} and --k `auto` or 1 .. --kmax")
     located = None
     if locs is not None:
-        locs = np.asarray(locs, dtype=np.float64).reshape(N, 2)
-        located = ~np.isnan(locs).any(axis=1)
-        if not located.any():
-            raise SystemExit(f"{PROG}: no sample of --sample_data has a location: nothing to place from")
+        locs, located = B.located_mask(locs, N, PROG)
     if not host:
         B.require_gpu(PROG, LAUNCH)
     _, first = site_gaps(chrom, pos, K, uniform)                    # refuses positions that descend inside a chromosome
@@ -341,25 +335,11 @@ def ibd(hap, c, P, samples, locs, chrom=None, pos=None, out=None, params=Params(
            "gap_sites": par.gap_sites, "gap_length": None if par.gap_len >= NO_LIMIT else par.gap_len, "min_length": par.min_len,
            "uniform": bool(flat), "segments": int(C[upper].sum()), "pairs_sharing": int(upper.sum()),
            "mean_length": B.num(shared.mean()) if len(shared) else None, "median_length": B.num(np.median(shared)) if len(shared) else None}
-    head, lines, xy, placed_own = {"N": int(N), "K": int(K), "P": int(P)}, [], None, {}
+    xy, head, placed_own, lines = None, {}, {}, []
     if located is not None:
-        kmax_used = int(min(kmax, located.sum()))
-        nbr, weight = B.top_donors(S.astype(np.float64), located, kmax_used)
-        placed = B.placements(nbr, weight, locs)
-        try:
-            k_auto, med = B.choose_smallest_median(placed, locs, located, longlat, NOTHING_TO_CHOOSE_BY)
-        except ValueError as e:
-            raise SystemExit(f"{PROG}: {e}") from None
-        k_used = min(k_auto if k == "auto" else int(k), kmax_used)
-        xy = placed[k_used - 1]
-        head, lines = B.placement_summary(c, P, located, xy, locs, longlat, "IBD")
-        placed_own = {"kmax": kmax_used, "k": int(k_used), "k_auto": int(k_auto), "k_chosen_by": "auto" if k == "auto" else "--k",
-                      "median_error_by_k": [B.num(v) for v in med]}
-        lines = [f"k = {k_used} ({placed_own['k_chosen_by']}; leave-one-out median error by k, k = 1 .. {kmax_used}, smallest at "
-                 f"k = {k_auto})", *lines]
-    summary = {**{key: head[key] for key in (HEAD if "n_located" in head else ("N", "K", "P"))},
-               **{key: own[key] for key in OWN}, **{key: placed_own[key] for key in PLACED if key in placed_own}}
-    summary["path"] = "host" if host else "device"
+        xy, head, placed_own, lines, _, _ = B.place_by_weight(PROG, S.astype(np.float64), located, kmax, k, c, P, locs, located, longlat,
+                                                              "IBD", NOTHING_TO_CHOOSE_BY)
+    summary = B.assemble_summary(head or {"N": int(N), "K": int(K), "P": int(P)}, own, placed_own, HEAD, OWN, PLACED, host)
     lines = [f"{N} samples, {K} sites: {own['segments']} segments between {H} haplotypes, {own['pairs_sharing']} sample pairs share, "
              f"median shared length {own['median_length']!r}", *lines]
     if out is not None:
@@ -368,8 +348,7 @@ def ibd(hap, c, P, samples, locs, chrom=None, pos=None, out=None, params=Params(
             f"{samples[s]}\t{samples[t]}\t{C[s, t]}\t{S[s, t]}\t{L[s, t]}\n" for s, t in zip(s_idx, t_idx)))
         write_atomic(out + "_ibd_summary.json", json.dumps(summary, indent=1) + "\n")
         if xy is not None:
-            frame = pd.DataFrame({"x": xy[:, 0], "y": xy[:, 1], "sampleID": samples.astype(object)})
-            write_atomic(out + "_ibd_locs.txt", lambda fh: frame.to_csv(fh, index=False))
+            B.write_locs(out + "_ibd_locs.txt", xy, samples)
         if keep_segments:
             where = np.arange(K, dtype=np.int64) if pos is None else np.asarray(pos, dtype=np.int64)
             names = np.full(K, ".", dtype=object) if chrom is None else np.asarray(chrom).astype(str)
@@ -400,9 +379,7 @@ def _own_arguments(p):
     p.add_argument("--gap_length", default=None, type=int, help="length between two joined runs at most (default: no limit)")
     p.add_argument("--min_length", default=0, type=int, help="length a segment must span (default 0)")
     p.add_argument("--uniform", default=False, action="store_true", help="lengths in sites: the coordinate of a site is its index")
-    p.add_argument("--k", default="auto", help="sharing samples averaged: a number, or `auto` (default): the k in 1 .. --kmax with "
-                                               "the smallest leave-one-out median error")
-    p.add_argument("--kmax", default=16, type=int, help=f"largest k tried (default 16, at most {KMAX_LIMIT})")
+    B.add_k_arguments(p, 16, "sharing samples")
     p.add_argument("--longlat", default=False, action="store_true",
                    help="x / y are longitude / latitude degrees: errors are great-circle km (the mean stays planar)")
     p.add_argument("--keep_segments", default=False, action="store_true", help="write every segment to {out}_ibd_segments.txt")
@@ -422,29 +399,14 @@ def build_parser():
 def main(argv=None):
     parser = build_parser()
     a = B.parse_args(parser, argv)
-    if a.k != "auto":
-        try:
-            a.k = int(a.k)
-        except ValueError:
-            parser.error("--k must be `auto` or a whole number")
-    if not 1 <= a.kmax <= KMAX_LIMIT:
-        parser.error(f"--kmax must be 1 .. {KMAX_LIMIT}")
-    if a.k != "auto" and not 1 <= a.k <= a.kmax:
-        parser.error(f"--k must be `auto` or 1 .. --kmax ({a.kmax})")
-    if not a.budget_gb > 0:
-        parser.error("--budget_gb must be positive")
-    c, P, samples, locs, idx, chrom, pos, gt = B.prelude(parser, a, LAUNCH, sites=True, phase=True)
-    from . import genotypes as G
+    B.check_k(parser, a)
+    B.check_budget(parser, a)
+    hap, c, P, samples, locs, chrom, pos = B.haplotype_prelude(parser, a, LAUNCH, "segments are sought between the two haplotypes a sample "
+                                                               "of ploidy 2 has")
     try:
-        if P != 2:
-            raise ValueError(f"calls of ploidy {P}: segments are sought between the two haplotypes a sample of ploidy 2 has")
-        order = np.argsort(idx, kind="stable")                         # a --max_SNPs draw comes in drawn order
-        idx = np.asarray(idx)[order]
-        chrom, pos = (None if t is None else np.asarray(t)[order] for t in (chrom, pos))
-        hap, _ = B.count_matrix_sites(G.haplotypes(np.asarray(gt)), idx)
         params = Params(a.seed_sites, a.seed_length, a.extend_sites, a.gap_sites, NO_LIMIT if a.gap_length is None else a.gap_length,
                         a.min_length)
-        ibd(hap, np.ascontiguousarray(c[:, order]), P, samples, locs, chrom, pos, a.out, params, a.uniform, a.k, a.kmax, a.longlat,
+        ibd(hap, c, P, samples, locs, chrom, pos, a.out, params, a.uniform, a.k, a.kmax, a.longlat,
             a.keep_segments, a.keep_matrix, a.host, a.silence, budget=int(a.budget_gb * (1 << 30)))
     except ValueError as e:
         raise SystemExit(f"{PROG}: {e}") from None

@@ -210,7 +210,7 @@ def band_device(ct, W, reach=None, thr=0.2, want_sums=True, want_r2=True, pitch=
     """(over, sums, r2) from one loc_ld_band launch; sums / r2 None where not wanted.  pitch / pad_fill as baselines.padded.
     fill: a byte the output buffers hold before the launch (tests: the launch must define every element)."""
     import torch
-    from . import _lib
+    from . import _device as D, _lib
     lib = _lib.load()
     ct = np.ascontiguousarray(ct, dtype=np.int8)
     K, N = ct.shape
@@ -220,8 +220,8 @@ def band_device(ct, W, reach=None, thr=0.2, want_sums=True, want_r2=True, pitch=
     if not buf.size:
         buf = np.full((1, max(buf.shape[1], 16)), -1, dtype=np.int8)      # no site: the launcher still wants a buffer
     with torch.cuda.device(device):
-        d_ct = torch.from_numpy(buf).to(device)
-        d_reach = None if reach is None else torch.from_numpy(np.ascontiguousarray(reach, dtype=np.int32).reshape(K)).to(device)
+        d_ct = D.put(buf, np.int8, device)
+        d_reach = None if reach is None else D.put(np.reshape(reach, K), np.int32, device)
         if d_reach is not None and K == 0:
             d_reach = torch.zeros(1, dtype=torch.int32, device=device)
         d_over = torch.empty((max(K, 1), words), dtype=torch.int32, device=device)
@@ -233,8 +233,7 @@ def band_device(ct, W, reach=None, thr=0.2, want_sums=True, want_r2=True, pitch=
                     d.view(torch.uint8).fill_(int(fill))
         _lib.check(lib.loc_ld_band(d_ct.data_ptr(), K, N, buf.shape[1], W, None if d_reach is None else d_reach.data_ptr(),
                                    float(thr), d_over.data_ptr(), None if d_sums is None else d_sums.data_ptr(),
-                                   None if d_r2 is None else d_r2.data_ptr(), torch.cuda.current_stream().cuda_stream),
-                   "loc_ld_band")
+                                   None if d_r2 is None else d_r2.data_ptr(), D.stream()), "loc_ld_band")
         over = d_over.cpu().numpy()[:K].view(np.uint32)
         return over, None if d_sums is None else d_sums.cpu().numpy()[:K], None if d_r2 is None else d_r2.cpu().numpy()[:K]
 

@@ -163,7 +163,7 @@ def windows_batches(c, mean, scale, win, batch_bytes=BATCH_BYTES, pitch=None, pa
     """Yields (w0, g float32 [n][N][N]) batch by batch: c, mean and scale are uploaded once, every batch is one loc_grm_windows
     launch and one download.  g_fill: a float32 bit pattern g holds before the launch (tests)."""
     import torch
-    from . import _lib
+    from . import _device as D, _lib
     lib = _lib.load()
     c = np.ascontiguousarray(c, dtype=np.int8)
     N, K = c.shape
@@ -174,11 +174,10 @@ def windows_batches(c, mean, scale, win, batch_bytes=BATCH_BYTES, pitch=None, pa
         d_g = torch.empty((per, max(N, 1), max(N, 1)), dtype=torch.float32, device=device)
         for w0 in range(0, len(win), per):
             n = min(per, len(win) - w0)
-            d_win = torch.from_numpy(win[w0:w0 + n]).to(device)
-            if g_fill is not None:
-                d_g.view(torch.int32).fill_(int(np.array(g_fill, dtype=np.uint32).view(np.int32)))
+            d_win = D.put(win[w0:w0 + n], np.int64, device)
+            D.prefill((d_g,), g_fill)
             _lib.check(lib.loc_grm_windows(d_c.data_ptr(), N, K, pitch, d_mean.data_ptr(), d_scale.data_ptr(), d_win.data_ptr(), n,
-                                           d_g.data_ptr(), torch.cuda.current_stream().cuda_stream), "loc_grm_windows")
+                                           d_g.data_ptr(), D.stream()), "loc_grm_windows")
             yield w0, d_g[:n].cpu().numpy()[:, :N, :N]
 
 

@@ -36,7 +36,6 @@ from ._files import write_atomic
 
 TILE = _abi.LOC_IBS_TILE
 BLOCK = _abi.LOC_IBS_BLOCK
-KMAX_LIMIT = 64
 PROG = "locator_amd.neighbors"
 LAUNCH = "the pair statistics are one loc_ibs_pairs launch"
 NOTHING_TO_CHOOSE_BY = "no located sample has a located neighbour: nothing to choose k by"
@@ -84,19 +83,19 @@ def pairs_planes(c):
 def pairs_device(c, k_groups=0, pitch=None, pad_fill=-1, device="cuda:0", keep_on_device=False):
     """pairs_host's answers from one loc_ibs_pairs launch.  keep_on_device: the two int32 tensors, not NumPy arrays."""
     import torch
-    from . import _lib
+    from . import _device as D, _lib
     lib = _lib.load()
     c = B.check_counts(c, 2)
     N, K = c.shape
     buf = B.padded(c, pitch, pad_fill)
     with torch.cuda.device(device):
-        d_c = torch.from_numpy(buf).to(device)
+        d_c = D.put(buf, np.int8, device)
         d_d = torch.empty((max(N, 1), max(N, 1)), dtype=torch.int32, device=device)
         d_n = torch.empty_like(d_d)
         work_bytes = int(lib.loc_ibs_work_bytes(N, K, int(k_groups)))
         work = torch.empty(max(work_bytes, 1), dtype=torch.uint8, device=device)
         _lib.check(lib.loc_ibs_pairs(d_c.data_ptr(), N, K, buf.shape[1], int(k_groups), d_d.data_ptr(), d_n.data_ptr(),
-                                     work.data_ptr(), work_bytes, torch.cuda.current_stream().cuda_stream), "loc_ibs_pairs")
+                                     work.data_ptr(), work_bytes, D.stream()), "loc_ibs_pairs")
         if keep_on_device:
             torch.cuda.synchronize()
             return d_d, d_n
@@ -134,17 +133,16 @@ def knn_host(d, n, P, candidate, kmax):
 def knn_device(d_d, d_n, N, P, candidate, kmax, device="cuda:0"):
     """knn_host's answers from one loc_ibs_knn launch; d_d, d_n are NumPy arrays or the device tensors of pairs_device."""
     import torch
-    from . import _lib
+    from . import _device as D, _lib
     lib = _lib.load()
     with torch.cuda.device(device):
         if not torch.is_tensor(d_d):
-            d_d = torch.from_numpy(np.ascontiguousarray(d_d, dtype=np.int32).reshape(N, N)).to(device)
-            d_n = torch.from_numpy(np.ascontiguousarray(d_n, dtype=np.int32).reshape(N, N)).to(device)
-        d_cand = torch.from_numpy(np.ascontiguousarray(np.asarray(candidate).astype(np.uint8))).to(device)
+            d_d, d_n = D.put(np.reshape(d_d, (N, N)), np.int32, device), D.put(np.reshape(d_n, (N, N)), np.int32, device)
+        d_cand = D.put(np.asarray(candidate).astype(np.uint8), np.uint8, device)
         d_nbr = torch.empty((max(N, 1), kmax), dtype=torch.int32, device=device)
         d_dist = torch.empty((max(N, 1), kmax), dtype=torch.float64, device=device)
         _lib.check(lib.loc_ibs_knn(d_d.data_ptr(), d_n.data_ptr(), N, int(P), d_cand.data_ptr(), int(kmax), d_nbr.data_ptr(),
-                                   d_dist.data_ptr(), torch.cuda.current_stream().cuda_stream), "loc_ibs_knn")
+                                   d_dist.data_ptr(), D.stream()), "loc_ibs_knn")
         return d_nbr.cpu().numpy()[:N], d_dist.cpu().numpy()[:N]
 
 
@@ -166,16 +164,12 @@ def neighbors(c, P, samples, locs, out=None, k="auto", kmax=32, longlat=False, c
               silence=False, device="cuda:0", extra=None):
     """The command's work for a count matrix: returns the summary dict and writes the output files when `out` is given.
     extra: entries appended to the summary (--ld_prune: what baselines.prelude recorded)."""
-    import pandas as pd
     c = B.check_counts(c, P)
     N, K = c.shape
     samples = np.asarray(samples).astype(str)
-    locs = np.asarray(locs, dtype=np.float64).reshape(N, 2)
-    located = ~np.isnan(locs).any(axis=1)
-    if not located.any():
-        raise SystemExit("locator_amd.neighbors: no sample of --sample_data has a location: nothing to place from")
-    if not 1 <= kmax <= KMAX_LIMIT:
-        raise SystemExit(f"locator_amd.neighbors: --kmax must be 1 .. {KMAX_LIMIT}")
+    locs, located = B.located_mask(locs, N, PROG)
+    if not 1 <= kmax <= B.KMAX_LIMIT:
+        raise SystemExit(f"locator_amd.neighbors: --kmax must be 1 .. {B.KMAX_LIMIT}")
     if k != "auto" and not 1 <= int(k) <= kmax:
         raise SystemExit(f"locator_amd.neighbors: --k must be `auto` or 1 .. --kmax ({kmax})")
     if host:
@@ -224,8 +218,7 @@ def neighbors(c, P, samples, locs, out=None, k="auto", kmax=32, longlat=False, c
     if pairs is not None:
         lines.append(f"{len(pairs[0])} pairs with IBS distance <= {close}")
     if out is not None:
-        frame = pd.DataFrame({"x": xy[:, 0], "y": xy[:, 1], "sampleID": samples.astype(object)})
-        write_atomic(out + "_knn_locs.txt", lambda fh: frame.to_csv(fh, index=False))
+        B.write_locs(out + "_knn_locs.txt", xy, samples)
         rows = ["sampleID\trank\tneighborID\tibs_dist\tn_sites\n"]
         for i in range(N):
             for r in range(kmax):
@@ -250,9 +243,7 @@ def neighbors(c, P, samples, locs, out=None, k="auto", kmax=32, longlat=False, c
 # ---------------------------------------------------------------- command
 
 def _own_arguments(p):
-    p.add_argument("--k", default="auto", help="neighbours averaged: a number, or `auto` (default): the k in 1 .. --kmax with "
-                                               "the smallest leave-one-out median error")
-    p.add_argument("--kmax", default=32, type=int, help=f"neighbours listed per sample and largest k tried (default 32, at most {KMAX_LIMIT})")
+    B.add_k_arguments(p, 32, "neighbours", "neighbours")
     p.add_argument("--longlat", default=False, action="store_true",
                    help="x / y are longitude / latitude degrees: errors are great-circle km (the mean stays planar)")
     p.add_argument("--close", default=None, type=float, metavar="T",
@@ -268,15 +259,7 @@ def build_parser():
 def main(argv=None):
     parser = build_parser()
     a = B.parse_args(parser, argv)
-    if a.k != "auto":
-        try:
-            a.k = int(a.k)
-        except ValueError:
-            parser.error("--k must be `auto` or a whole number")
-    if not 1 <= a.kmax <= KMAX_LIMIT:
-        parser.error(f"--kmax must be 1 .. {KMAX_LIMIT}")
-    if a.k != "auto" and not 1 <= a.k <= a.kmax:
-        parser.error(f"--k must be `auto` or 1 .. --kmax ({a.kmax})")
+    B.check_k(parser, a)
     if a.close is not None and not a.close >= 0:
         parser.error("--close must be a distance >= 0")
     c, P, samples, locs, _ = B.prelude(parser, a, LAUNCH)

@@ -64,7 +64,6 @@ from ._files import write_atomic
 
 MAX_HAPS = _abi.LOC_PAINT_MAX_HAPS
 THETA_MIN, THETA_MAX = 1e-7, 0.5
-KMAX_LIMIT = 64
 PROG = "locator_amd.paint"
 LAUNCH = "the recursions are loc_paint_copy launches"
 NOTHING_TO_CHOOSE_BY = "no located sample copies from a located donor: nothing to choose k by"
@@ -161,16 +160,15 @@ def copy_device(h, donor, owner, rec, rho, theta, block=0, pitch=None, pad_fill=
     """copy_host's answer from loc_paint_copy launches (share and chunks float32), the recipients in batches whose scratch
     stays within `budget` bytes.  fill: a 32-bit pattern that scratch and the outputs hold before a launch (tests)."""
     import torch
-    from . import _lib
+    from . import _device as D, _lib
     lib = _lib.load()
     h, dflag, owner, rec, rho = _check(h, donor, owner, rec, rho, theta)
     K, H, R = h.shape[0], len(dflag), len(rec)
     buf = B.padded(np.ascontiguousarray(h[:, :H]), pitch, pad_fill)
     t = torch
     with t.cuda.device(device):
-        put = lambda v, dt: t.from_numpy(np.ascontiguousarray(v, dtype=dt)).to(device)
-        d_h, d_donor, d_owner = t.from_numpy(buf).to(device), put(dflag, np.uint8), put(owner, np.int32)
-        d_rho = put(rho if K else np.zeros(1), np.float32)
+        d_h, d_donor, d_owner = D.put(buf, np.int8, device), D.put(dflag, np.uint8, device), D.put(owner, np.int32, device)
+        d_rho = D.put(rho if K else np.zeros(1), np.float32, device)
         one = int(lib.loc_paint_work_bytes(H, K, 1, int(block)))
         if one < 0:
             _lib.check(-1, "loc_paint_work_bytes")
@@ -179,21 +177,17 @@ def copy_device(h, donor, owner, rec, rho, theta, block=0, pitch=None, pad_fill=
         ll, n_donors = np.zeros(R), np.zeros(R, dtype=np.int32)
         for a in range(0, R, step):
             n = min(step, R - a)
-            d_rec = put(rec[a:a + n], np.int32)
+            d_rec = D.put(rec[a:a + n], np.int32, device)
             d_share = t.empty((n, H), dtype=t.float32, device=device)
             d_chunks = t.empty((n, H), dtype=t.float32, device=device)
             d_ll = t.empty(n, dtype=t.float64, device=device)
             d_nd = t.empty(n, dtype=t.int32, device=device)
-            work_bytes = int(lib.loc_paint_work_bytes(H, K, n, int(block)))
-            d_work = t.empty(max(work_bytes // 4, 4), dtype=t.float32, device=device)
-            if fill is not None:
-                bits = int(np.array(fill, dtype=np.uint32).view(np.int32))
-                for x in (d_work, d_share, d_chunks, d_ll, d_nd):
-                    x.view(t.int32).fill_(bits)
+            d_work, work_bytes = D.work_buffer(lib, "loc_paint_work_bytes", H, K, n, int(block), device=device, fill=fill)
+            D.prefill((d_share, d_chunks, d_ll, d_nd), fill)
             _lib.check(lib.loc_paint_copy(d_h.data_ptr(), H, K, int(buf.shape[1]), d_donor.data_ptr(), d_owner.data_ptr(),
                                           d_rec.data_ptr(), n, d_rho.data_ptr(), float(theta), int(block), d_share.data_ptr(),
                                           d_chunks.data_ptr(), d_ll.data_ptr(), d_nd.data_ptr(), d_work.data_ptr(), work_bytes,
-                                          t.cuda.current_stream().cuda_stream), "loc_paint_copy")
+                                          D.stream()), "loc_paint_copy")
             share[a:a + n], chunks[a:a + n] = d_share.cpu().numpy(), d_chunks.cpu().numpy()
             ll[a:a + n], n_donors[a:a + n] = d_ll.cpu().numpy(), d_nd.cpu().numpy()
             del d_work
@@ -301,7 +295,6 @@ def paint(hap, c, P, samples, locs, chrom=None, pos=None, out=None, switch=0.01,
     """The command's work for a site-major haplotype matrix hap [K][2N] (c: the count matrix of the same sites, for the shared
     summary entries): returns the summary dict and writes the output files when `out` is given.  locs None: no locations.
     dtype: the arithmetic of --host."""
-    import pandas as pd
     hap = np.ascontiguousarray(hap, dtype=np.int8)
     K, H = hap.shape
     N = H // 2
@@ -320,10 +313,7 @@ def paint(hap, c, P, samples, locs, chrom=None, pos=None, out=None, switch=0.01,
         raise SystemExit(f"{PROG}: --max_donors must be >= 1")
     located = None
     if locs is not None:
-        locs = np.asarray(locs, dtype=np.float64).reshape(N, 2)
-        located = ~np.isnan(locs).any(axis=1)
-        if not located.any():
-            raise SystemExit(f"{PROG}: no sample of --sample_data has a location: nothing to place from")
+        locs, located = B.located_mask(locs, N, PROG)
     pool = np.arange(N) if located is None else np.flatnonzero(located)
     donors = pool if max_donors is None else pool[::-(-len(pool) // max_donors)]
     if 2 * len(donors) + (2 if len(donors) < N else 0) > max_haps:
@@ -334,8 +324,8 @@ def paint(hap, c, P, samples, locs, chrom=None, pos=None, out=None, switch=0.01,
         theta = default_theta(2 * len(donors))
     if not THETA_MIN <= theta <= THETA_MAX:
         raise SystemExit(f"{PROG}: --theta must be {THETA_MIN} .. {THETA_MAX}")
-    if k != "auto" and not 1 <= int(k) <= kmax or not 1 <= kmax <= KMAX_LIMIT:
-        raise SystemExit(f"{PROG}: --kmax must be 1 .. {KMAX_LIMIT} and --k `auto` or 1 .. --kmax")
+    if k != "auto" and not 1 <= int(k) <= kmax or not 1 <= kmax <= B.KMAX_LIMIT:
+        raise SystemExit(f"{PROG}: --kmax must be 1 .. {B.KMAX_LIMIT} and --k `auto` or 1 .. --kmax")
     if host:
         copy = lambda *six: copy_host(*six, dtype=dtype)
     else:
@@ -357,29 +347,12 @@ def paint(hap, c, P, samples, locs, chrom=None, pos=None, out=None, switch=0.01,
     rho = switch_rates(lam, g, first)
     W, C, ll, nd, n_groups = sample_weights(copy, hap, donors, rho, theta, max_haps)
 
-    is_donor = np.isin(np.arange(N), donors)
-    kmax_used = int(min(kmax, len(donors)))
-    nbr, weight = top_donors(W, is_donor, kmax_used)
     own = {"H": int(H), "n_donor_haps": int(2 * len(donors)), "groups": int(n_groups), "theta": float(theta), "switch": float(lam),
            "uniform": bool(uniform or pos is None), "em_rounds": int(em_rounds), "em_recipients": int(2 * len(em_recipients)),
            "ll": B.num(ll.sum()), "mean_chunks": B.num(C.sum() / max(int((nd > 0).sum()), 1))}
-    shared, lines, xy, placed_own = {"N": int(N), "K": int(K), "P": int(P)}, [], None, {}
-    if located is not None:
-        placed = placements(nbr, weight, locs)
-        try:
-            k_auto, med = B.choose_smallest_median(placed, locs, located, longlat, NOTHING_TO_CHOOSE_BY)
-        except ValueError as e:
-            raise SystemExit(f"{PROG}: {e}") from None
-        k_used = min(k_auto if k == "auto" else int(k), kmax_used)
-        xy = placed[k_used - 1]
-        shared, lines = B.placement_summary(c, P, located, xy, locs, longlat, "copying")
-        placed_own = {"kmax": kmax_used, "k": int(k_used), "k_auto": int(k_auto), "k_chosen_by": "auto" if k == "auto" else "--k",
-                      "median_error_by_k": [B.num(v) for v in med]}
-        lines = [f"k = {k_used} ({placed_own['k_chosen_by']}; leave-one-out median error by k, k = 1 .. {kmax_used}, smallest at "
-                 f"k = {k_auto})", *lines]
-    summary = {**{key: shared[key] for key in (HEAD if "n_located" in shared else ("N", "K", "P"))},
-               **{key: own[key] for key in OWN}, **{key: placed_own[key] for key in PLACED if key in placed_own}}
-    summary["path"] = "host" if host else "device"
+    xy, head, placed_own, lines, nbr, weight = B.place_by_weight(PROG, W, np.isin(np.arange(N), donors), kmax, k, c, P, locs, located,
+                                                                 longlat, "copying", NOTHING_TO_CHOOSE_BY)
+    summary = B.assemble_summary(head or {"N": int(N), "K": int(K), "P": int(P)}, own, placed_own, HEAD, OWN, PLACED, host)
     lines = [f"{N} samples, {K} sites: {H} haplotypes copy from {2 * len(donors)} donor haplotypes in {n_groups} launch group(s)",
              f"theta {theta!r}, switch rate {lam!r} after {em_rounds} rounds, ll {own['ll']!r}, {own['mean_chunks']!r} chunks a "
              f"haplotype", *lines]
@@ -387,15 +360,14 @@ def paint(hap, c, P, samples, locs, chrom=None, pos=None, out=None, switch=0.01,
         write_atomic(out + "_paint_history.txt", "round\tswitch\tll\n" + "".join(f"{t}\t{l!r}\t{v!r}\n" for t, l, v in history))
         rows = ["sampleID\trank\tdonorID\tshare\n"]
         for s in range(N):
-            for r in range(kmax_used):
+            for r in range(nbr.shape[1]):
                 if nbr[s, r] < 0:
                     break
                 rows.append(f"{samples[s]}\t{r + 1}\t{samples[nbr[s, r]]}\t{float(weight[s, r] / 2)!r}\n")
         write_atomic(out + "_paint_donors.txt", "".join(rows))
         write_atomic(out + "_paint_summary.json", json.dumps(summary, indent=1) + "\n")
         if xy is not None:
-            frame = pd.DataFrame({"x": xy[:, 0], "y": xy[:, 1], "sampleID": samples.astype(object)})
-            write_atomic(out + "_paint_locs.txt", lambda fh: frame.to_csv(fh, index=False))
+            B.write_locs(out + "_paint_locs.txt", xy, samples)
         if keep_matrix:
             write_atomic(out + "_paint.npz", lambda fh: B.save_npz(fh, lengths=K * W / 2, counts=C, samples=samples), mode="wb")
     if not silence:
@@ -416,9 +388,7 @@ def _own_arguments(p):
     p.add_argument("--uniform", default=False, action="store_true", help="every site one mean gap from the one before it")
     p.add_argument("--max_donors", default=None, type=int, metavar="M", help="take every ceil(n / M)-th candidate sample as a donor")
     p.add_argument("--max_haps", default=MAX_HAPS, type=int, help=f"haplotype columns of a launch at most (default and limit {MAX_HAPS})")
-    p.add_argument("--k", default="auto", help="donor samples averaged: a number, or `auto` (default): the k in 1 .. --kmax with "
-                                               "the smallest leave-one-out median error")
-    p.add_argument("--kmax", default=16, type=int, help=f"donors listed per sample and largest k tried (default 16, at most {KMAX_LIMIT})")
+    B.add_k_arguments(p, 16, "donor samples", "donors")
     p.add_argument("--longlat", default=False, action="store_true",
                    help="x / y are longitude / latitude degrees: errors are great-circle km (the mean stays planar)")
     p.add_argument("--keep_matrix", default=False, action="store_true",
@@ -439,27 +409,11 @@ def build_parser():
 def main(argv=None):
     parser = build_parser()
     a = B.parse_args(parser, argv)
-    if a.k != "auto":
-        try:
-            a.k = int(a.k)
-        except ValueError:
-            parser.error("--k must be `auto` or a whole number")
-    if not 1 <= a.kmax <= KMAX_LIMIT:
-        parser.error(f"--kmax must be 1 .. {KMAX_LIMIT}")
-    if a.k != "auto" and not 1 <= a.k <= a.kmax:
-        parser.error(f"--k must be `auto` or 1 .. --kmax ({a.kmax})")
-    if not a.budget_gb > 0:
-        parser.error("--budget_gb must be positive")
-    c, P, samples, locs, idx, chrom, pos, gt = B.prelude(parser, a, LAUNCH, sites=True, phase=True)
-    from . import genotypes as G
+    B.check_k(parser, a)
+    B.check_budget(parser, a)
+    hap, c, P, samples, locs, chrom, pos = B.haplotype_prelude(parser, a, LAUNCH, "the copying model is built for two haplotypes a sample")
     try:
-        if P != 2:
-            raise ValueError(f"calls of ploidy {P}: the copying model is built for two haplotypes a sample")
-        order = np.argsort(idx, kind="stable")                         # a --max_SNPs draw comes in drawn order
-        idx = np.asarray(idx)[order]
-        chrom, pos = (None if t is None else np.asarray(t)[order] for t in (chrom, pos))
-        hap, _ = B.count_matrix_sites(G.haplotypes(np.asarray(gt)), idx)
-        paint(hap, np.ascontiguousarray(c[:, order]), P, samples, locs, chrom, pos, a.out, a.switch, a.em_rounds, a.em_sample, a.theta,
+        paint(hap, c, P, samples, locs, chrom, pos, a.out, a.switch, a.em_rounds, a.em_sample, a.theta,
               a.uniform, a.max_donors, a.max_haps, a.k, a.kmax, a.longlat, a.keep_matrix, a.host, a.silence,
               budget=int(a.budget_gb * (1 << 30)), dtype=np.dtype(a.host_dtype).type)
     except ValueError as e:

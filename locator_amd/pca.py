@@ -137,39 +137,33 @@ def report_loadings(T, K_used, lam):
 
 def _upload(c, mean, scale, pitch=None, pad_fill=-1, device="cuda:0"):
     import torch
+    from . import _device as D
     buf = B.padded(c, pitch, pad_fill)
     with torch.cuda.device(device):
-        return (torch.from_numpy(buf).to(device), torch.from_numpy(np.ascontiguousarray(mean, dtype=np.float32)).to(device),
-                torch.from_numpy(np.ascontiguousarray(scale, dtype=np.float32)).to(device), int(buf.shape[1]))
+        return D.put(buf, np.int8, device), D.put(mean, np.float32, device), D.put(scale, np.float32, device), int(buf.shape[1])
 
 
 def grm_device(c, mean, scale, k_groups=0, pitch=None, pad_fill=-1, device="cuda:0", work_fill=None, on_device=None):
     """grm_host's matrix from one loc_grm_pairs launch, float64 [N][N].  work_fill: a float32 bit pattern the scratch holds
     before the launch (tests); on_device: the tensors of _upload, to share them with loadings_device."""
     import torch
-    from . import _lib
+    from . import _device as D, _lib
     lib = _lib.load()
     c = np.ascontiguousarray(c, dtype=np.int8)
     N, K = c.shape
     d_c, d_mean, d_scale, pitch = on_device or _upload(c, mean, scale, pitch, pad_fill, device)
     with torch.cuda.device(device):
         d_g = torch.empty((max(N, 1), max(N, 1)), dtype=torch.float64, device=device)
-        work_bytes = int(lib.loc_grm_work_bytes(N, K, int(k_groups)))
-        if work_bytes < 0:
-            _lib.check(-1, "loc_grm_work_bytes")
-        work = torch.empty(max(work_bytes // 4, 4), dtype=torch.float32, device=device)
-        if work_fill is not None:
-            work.view(torch.int32).fill_(int(np.array(work_fill, dtype=np.uint32).view(np.int32)))
+        work, work_bytes = D.work_buffer(lib, "loc_grm_work_bytes", N, K, int(k_groups), device=device, fill=work_fill)
         _lib.check(lib.loc_grm_pairs(d_c.data_ptr(), N, K, pitch, d_mean.data_ptr(), d_scale.data_ptr(), int(k_groups),
-                                     d_g.data_ptr(), work.data_ptr(), work_bytes, torch.cuda.current_stream().cuda_stream),
-                   "loc_grm_pairs")
+                                     d_g.data_ptr(), work.data_ptr(), work_bytes, D.stream()), "loc_grm_pairs")
         return d_g.cpu().numpy()[:N, :N]
 
 
 def loadings_device(c, mean, scale, U32, pitch=None, pad_fill=-1, device="cuda:0", on_device=None):
     """loadings_host's matrix from one loc_pca_loadings launch, float32 [K][npc]."""
     import torch
-    from . import _lib
+    from . import _device as D, _lib
     lib = _lib.load()
     c = np.ascontiguousarray(c, dtype=np.int8)
     N, K = c.shape
@@ -177,10 +171,10 @@ def loadings_device(c, mean, scale, U32, pitch=None, pad_fill=-1, device="cuda:0
     npc = U32.shape[1]
     d_c, d_mean, d_scale, pitch = on_device or _upload(c, mean, scale, pitch, pad_fill, device)
     with torch.cuda.device(device):
-        d_u = torch.from_numpy(U32).to(device)
+        d_u = D.put(U32, np.float32, device)
         d_t = torch.empty((max(K, 1), npc), dtype=torch.float32, device=device)
         _lib.check(lib.loc_pca_loadings(d_c.data_ptr(), N, K, pitch, d_mean.data_ptr(), d_scale.data_ptr(), d_u.data_ptr(), npc,
-                                        d_t.data_ptr(), torch.cuda.current_stream().cuda_stream), "loc_pca_loadings")
+                                        d_t.data_ptr(), D.stream()), "loc_pca_loadings")
         return d_t.cpu().numpy()[:K]
 
 

@@ -221,7 +221,7 @@ def nearest_host(pts3, verts3, chunk=1 << 21):
 def assign_device(pts, rs_or_verts, ring_off=None, ring_region=None, ring_bbox=None, n_regions=None, device="cuda:0"):
     """assign_host's answers from one loc_region_assign launch; takes a RegionSet or its arrays."""
     import torch
-    from . import _lib
+    from . import _device as D, _lib
     if isinstance(rs_or_verts, RegionSet):
         rs = rs_or_verts
         verts, ring_off, ring_region, ring_bbox, n_regions = rs.verts, rs.ring_off, rs.ring_region, rs.ring_bbox, len(rs.names)
@@ -239,28 +239,28 @@ def assign_device(pts, rs_or_verts, ring_off=None, ring_region=None, ring_bbox=N
     if n_regions is None:
         n_regions = int(ring_region.max()) + 1 if n_rings else 0
     with torch.cuda.device(device):
-        d = [torch.from_numpy(a).to(device) for a in (pts, verts, ring_off, ring_region, ring_bbox)]
+        d = [D.put(a, None, device) for a in (pts, verts, ring_off, ring_region, ring_bbox)]
         d_reg = torch.empty(max(len(pts), 1), dtype=torch.int32, device=device)
         d_cnt = torch.empty(max(len(pts), 1), dtype=torch.int32, device=device)
         _lib.check(lib.loc_region_assign(d[0].data_ptr(), len(pts), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
                                          d[4].data_ptr(), n_rings, int(n_regions), d_reg.data_ptr(), d_cnt.data_ptr(),
-                                         torch.cuda.current_stream().cuda_stream), "loc_region_assign")
+                                         D.stream()), "loc_region_assign")
         return d_reg.cpu().numpy()[:len(pts)], d_cnt.cpu().numpy()[:len(pts)]
 
 
 def nearest_device(pts3, verts3, device="cuda:0"):
     """nearest_host's answers from one loc_region_nearest launch."""
     import torch
-    from . import _lib
+    from . import _device as D, _lib
     lib = _lib.load()
     pts3 = np.ascontiguousarray(pts3, dtype=np.float64).reshape(-1, 3)
     verts3 = np.ascontiguousarray(verts3, dtype=np.float64).reshape(-1, 3)
     with torch.cuda.device(device):
-        d_p, d_v = torch.from_numpy(pts3).to(device), torch.from_numpy(verts3).to(device)
+        d_p, d_v = D.put(pts3, np.float64, device), D.put(verts3, np.float64, device)
         d_k = torch.empty(max(len(pts3), 1), dtype=torch.int64, device=device)
         d_d = torch.empty(max(len(pts3), 1), dtype=torch.float64, device=device)
         _lib.check(lib.loc_region_nearest(d_p.data_ptr(), len(pts3), d_v.data_ptr(), len(verts3), d_k.data_ptr(),
-                                          d_d.data_ptr(), torch.cuda.current_stream().cuda_stream), "loc_region_nearest")
+                                          d_d.data_ptr(), D.stream()), "loc_region_nearest")
         return d_k.cpu().numpy()[:len(pts3)], d_d.cpu().numpy()[:len(pts3)]
 
 

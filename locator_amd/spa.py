@@ -284,21 +284,20 @@ def fold_of(located, folds):
 def fit_device(ct, P, xy, w, ridge, iters, pitch=None, pad_fill=-1, device="cuda:0", on_device=None):
     """fit_host's answer from one loc_spa_fit launch.  on_device: (tensor of the padded ct, pitch), to share an upload."""
     import torch
-    from . import _lib
+    from . import _device as D, _lib
     lib = _lib.load()
     ct = np.ascontiguousarray(ct, dtype=np.int8)
     K, N = ct.shape
     with torch.cuda.device(device):
         if on_device is None:
             buf = B.padded(ct, pitch, pad_fill)
-            on_device = (torch.from_numpy(buf).to(device), int(buf.shape[1]))
+            on_device = (D.put(buf, np.int8, device), int(buf.shape[1]))
         d_ct, pitch = on_device
-        d_xy = torch.from_numpy(np.ascontiguousarray(xy, dtype=np.float32).reshape(N, 2)).to(device)
-        d_w = torch.from_numpy(np.ascontiguousarray(w, dtype=np.uint8).reshape(N)).to(device)
+        d_xy, d_w = D.put(np.reshape(xy, (N, 2)), np.float32, device), D.put(np.reshape(w, N), np.uint8, device)
         d_theta = torch.full((max(K, 1), 4), float("nan"), dtype=torch.float32, device=device)
         d_used = torch.full((max(K, 1),), 255, dtype=torch.uint8, device=device)
         _lib.check(lib.loc_spa_fit(d_ct.data_ptr(), K, N, pitch, int(P), d_xy.data_ptr(), d_w.data_ptr(), float(ridge), int(iters),
-                                   d_theta.data_ptr(), d_used.data_ptr(), torch.cuda.current_stream().cuda_stream), "loc_spa_fit")
+                                   d_theta.data_ptr(), d_used.data_ptr(), D.stream()), "loc_spa_fit")
         return d_theta.cpu().numpy()[:K], d_used.cpu().numpy()[:K]
 
 
@@ -306,7 +305,7 @@ def grid_device(c, P, theta, used, gx, gy, k_groups=0, pitch=None, pad_fill=-1, 
     """grid_host's matrix from one loc_spa_grid launch, float64 [Q][G].  fill: a float32 bit pattern that scratch and (twice,
     as a float64) ll hold before the launch (tests); on_device: (tensor of the padded c, pitch)."""
     import torch
-    from . import _lib
+    from . import _device as D, _lib
     lib = _lib.load()
     c = np.ascontiguousarray(c, dtype=np.int8)
     Q, K = c.shape
@@ -314,26 +313,18 @@ def grid_device(c, P, theta, used, gx, gy, k_groups=0, pitch=None, pad_fill=-1, 
     with torch.cuda.device(device):
         if on_device is None:
             buf = B.padded(c, pitch, pad_fill)
-            on_device = (torch.from_numpy(buf).to(device), int(buf.shape[1]))
+            on_device = (D.put(buf, np.int8, device), int(buf.shape[1]))
         d_c, pitch = on_device
-        d_theta = torch.from_numpy(np.ascontiguousarray(theta, dtype=np.float32).reshape(K, 4)).to(device)
-        d_used = torch.from_numpy(np.ascontiguousarray(used, dtype=np.uint8).reshape(K)).to(device)
+        d_theta, d_used = D.put(np.reshape(theta, (K, 4)), np.float32, device), D.put(np.reshape(used, K), np.uint8, device)
         if K == 0:
             d_theta, d_used = torch.zeros(4, dtype=torch.float32, device=device), torch.zeros(1, dtype=torch.uint8, device=device)
-        d_gx = torch.from_numpy(np.ascontiguousarray(gx, dtype=np.float32)).to(device)
-        d_gy = torch.from_numpy(np.ascontiguousarray(gy, dtype=np.float32)).to(device)
+        d_gx, d_gy = D.put(gx, np.float32, device), D.put(gy, np.float32, device)
         d_ll = torch.empty((max(Q, 1), G), dtype=torch.float64, device=device)
-        work_bytes = int(lib.loc_spa_grid_work_bytes(Q, K, G, int(k_groups)))
-        if work_bytes < 0:
-            _lib.check(-1, "loc_spa_grid_work_bytes")
-        work = torch.empty(max(work_bytes // 4, 4), dtype=torch.float32, device=device)
-        if fill is not None:
-            bits = int(np.array(fill, dtype=np.uint32).view(np.int32))
-            work.view(torch.int32).fill_(bits)
-            d_ll.view(torch.int32).fill_(bits)
+        work, work_bytes = D.work_buffer(lib, "loc_spa_grid_work_bytes", Q, K, G, int(k_groups), device=device, fill=fill)
+        D.prefill((d_ll,), fill)
         _lib.check(lib.loc_spa_grid(d_c.data_ptr(), Q, K, pitch, int(P), d_theta.data_ptr(), d_used.data_ptr(), d_gx.data_ptr(),
-                                    d_gy.data_ptr(), G, int(k_groups), d_ll.data_ptr(), work.data_ptr(), work_bytes,
-                                    torch.cuda.current_stream().cuda_stream), "loc_spa_grid")
+                                    d_gy.data_ptr(), G, int(k_groups), d_ll.data_ptr(), work.data_ptr(), work_bytes, D.stream()),
+                   "loc_spa_grid")
         return d_ll.cpu().numpy()[:Q]
 
 
@@ -373,9 +364,10 @@ def spa(c, P, samples, locs, out=None, folds=10, grid=64, pad=0.1, ridge=1.0, it
     else:
         B.require_gpu(PROG, LAUNCH)
         import torch
+        from . import _device as D
         with torch.cuda.device(device):
             buf = B.padded(ct)
-            d_ct = (torch.from_numpy(buf).to(device), int(buf.shape[1]))
+            d_ct = (D.put(buf, np.int8, device), int(buf.shape[1]))
 
         def fit(w):
             return fit_device(ct, P, xy, w, ridge, iters, device=device, on_device=d_ct)

@@ -155,6 +155,28 @@ def test_missing_header_is_an_error_that_names_the_path(repo_root, tmp_path):
     assert r.returncode != 0 and os.path.join(str(tmp_path), "include", "locator_hip.h") in r.stderr
 
 
+def test_an_extension_header_that_declares_what_it_may_not_is_refused_by_name(repo_root, tmp_path):
+    import shutil
+    pkg = tmp_path / "locator_amd"
+    pkg.mkdir()
+    (pkg / "__init__.py").write_text("")
+    shutil.copy(os.path.join(repo_root, "locator_amd", "_abi.py"), pkg / "_abi.py")
+    shutil.copytree(os.path.join(repo_root, "include"), tmp_path / "include")
+    run = lambda: subprocess.run([sys.executable, "-c", "import locator_amd._abi"], cwd=tmp_path, capture_output=True, text=True)
+    assert run().returncode == 0
+    for header, addition in (("locator_hip_ibd.h", "int loc_ibs_knn(int N);"),          # a function of locator_hip_neighbors.h
+                             ("locator_hip_pca.h", "int loc_version(void);"),           # a function of the main header
+                             ("locator_hip_paint.h", "#define LOC_PAINT_TILE 2.5"),     # no integer
+                             ("locator_hip_paint.h", "#define LOC_IBD_TILE 2"),         # a constant outside its prefix
+                             ("locator_hip_query.h", "#define LOC_QUERY_TILE 64")):     # this header may declare functions only
+        path = tmp_path / "include" / header
+        text = path.read_text()
+        path.write_text(text + "\n" + addition + "\n")
+        r = run()
+        assert r.returncode != 0 and "ValueError" in r.stderr and str(path) + " may declare" in r.stderr, (header, addition, r.stderr)
+        path.write_text(text)
+
+
 def test_dims_and_layout():
     d = _lib.make_dims(5830, 256, 10)
     assert (d.K, d.Kp, d.H, d.Hp, d.L, d.n_pre) == (5830, 5856, 256, 256, 10, 5)

@@ -5,7 +5,6 @@ import ctypes as C
 import json
 import math
 import os
-import re
 
 import numpy as np
 import pytest
@@ -16,29 +15,15 @@ from tests import admix_util as U
 
 
 # ------------------------------------------------------------------ the binding
-def test_admix_header_is_bound_as_the_other_headers_are(repo_root):
-    from locator_amd import _abi, _lib
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(repo_root, "include", "locator_hip_admix.h")).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(loc_[a-z0-9_]+)\s*\(", src)))
-    assert names == ["loc_admix_step", "loc_admix_work_bytes"] == sorted(_abi.ADMIX_PROTOTYPES)
-    assert _lib.ADMIX_SIGNATURES is _abi.ADMIX_PROTOTYPES
-    others = (set(_abi.PROTOTYPES) | set(_abi.EXT_PROTOTYPES) | set(_abi.REGION_PROTOTYPES) | set(_abi.NEIGHBOR_PROTOTYPES)
-              | set(_abi.PCA_PROTOTYPES) | set(_abi.LD_PROTOTYPES) | set(_abi.SPA_PROTOTYPES))
-    assert not set(names) & others
+def test_admix_header_is_bound_as_the_other_headers_are():
+    from locator_amd import _abi
+    from tests.abi_util import check_extension
     vp, i64, i = C.c_void_p, C.c_int64, C.c_int
-    assert _abi.ADMIX_PROTOTYPES["loc_admix_work_bytes"] == (i64, [i, i64, i, i])
-    assert _abi.ADMIX_PROTOTYPES["loc_admix_step"] == (i, [vp, i, i64, i64, i, i, vp, vp, vp, vp, vp, i, vp, i64, vp])
-    assert set(_abi.ADMIX_CONSTANTS) == {"LOC_ADMIX_MAX_POPS", "LOC_ADMIX_LL_RUN", "LOC_ADMIX_TILE", "LOC_ADMIX_BLOCK",
-                                         "LOC_ADMIX_SPLIT"}
-    assert all(isinstance(v, int) and v > 0 for v in _abi.ADMIX_CONSTANTS.values())
+    check_extension("admix", {"loc_admix_work_bytes": (i64, [i, i64, i, i]),
+                              "loc_admix_step": (i, [vp, i, i64, i64, i, i, vp, vp, vp, vp, vp, i, vp, i64, vp])},
+                    {"LOC_ADMIX_MAX_POPS", "LOC_ADMIX_LL_RUN", "LOC_ADMIX_TILE", "LOC_ADMIX_BLOCK", "LOC_ADMIX_SPLIT"})
     assert (_abi.LOC_ADMIX_MAX_POPS, _abi.LOC_ADMIX_LL_RUN, _abi.LOC_ADMIX_TILE, _abi.LOC_ADMIX_BLOCK) == (
         A.MAX_POPS, A.LL_RUN, A.TILE, A.BLOCK) == (16, 1024, 64, 64)
-    assert not set(_abi.ADMIX_CONSTANTS) & (set(_abi.CONSTANTS) | set(_abi.REGION_CONSTANTS) | set(_abi.NEIGHBOR_CONSTANTS)
-                                            | set(_abi.PCA_CONSTANTS) | set(_abi.LD_CONSTANTS) | set(_abi.SPA_CONSTANTS))
-    lib = _lib.load()
-    for name in names:
-        fn = getattr(lib, name)
-        assert fn.restype is _abi.ADMIX_PROTOTYPES[name][0] and list(fn.argtypes) == _abi.ADMIX_PROTOTYPES[name][1]
 
 
 # ------------------------------------------------------------------ step_host

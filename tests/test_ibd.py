@@ -4,7 +4,6 @@ samples, the --host command on a cut of the golden VCF with its refusals, the ho
 import ctypes as C
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -102,27 +101,15 @@ def test_pack_host_bit_by_bit():
 
 
 # ------------------------------------------------------------------ the binding
-def test_ibd_header_is_bound_as_the_other_headers_are(repo_root):
-    from locator_amd import _abi, _lib
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(repo_root, "include", "locator_hip_ibd.h")).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(loc_[a-z0-9_]+)\s*\(", src)))
-    assert names == ["loc_ibd_fill", "loc_ibd_pack", "loc_ibd_scan"] == sorted(_abi.IBD_PROTOTYPES)
-    assert _lib.IBD_SIGNATURES is _abi.IBD_PROTOTYPES
-    others = (set(_abi.PROTOTYPES) | set(_abi.EXT_PROTOTYPES) | set(_abi.REGION_PROTOTYPES) | set(_abi.NEIGHBOR_PROTOTYPES)
-              | set(_abi.PCA_PROTOTYPES) | set(_abi.LD_PROTOTYPES) | set(_abi.SPA_PROTOTYPES) | set(_abi.ADMIX_PROTOTYPES)
-              | set(_abi.LOCALPCA_PROTOTYPES) | set(_abi.PAINT_PROTOTYPES))
-    assert not set(names) & others
+def test_ibd_header_is_bound_as_the_other_headers_are():
+    from locator_amd import _abi
+    from tests.abi_util import check_extension
     vp, i64, i = C.c_void_p, C.c_int64, C.c_int
     scan = [vp, i64, i, i64, vp, vp, vp, i, i, i64, i64, i64, i64, i64, i64]
-    assert _abi.IBD_PROTOTYPES["loc_ibd_pack"] == (i, [vp, i, i64, i64, vp, i64, vp])
-    assert _abi.IBD_PROTOTYPES["loc_ibd_scan"] == (i, scan + [vp, vp, vp, vp])
-    assert _abi.IBD_PROTOTYPES["loc_ibd_fill"] == (i, scan + [vp, i64, vp, vp, vp])
-    assert set(_abi.IBD_CONSTANTS) == {"LOC_IBD_MAX_HAPS", "LOC_IBD_MAX_GAP", "LOC_IBD_PACK_COLS", "LOC_IBD_BLOCK"}
+    check_extension("ibd", {"loc_ibd_pack": (i, [vp, i, i64, i64, vp, i64, vp]), "loc_ibd_scan": (i, scan + [vp, vp, vp, vp]),
+                            "loc_ibd_fill": (i, scan + [vp, i64, vp, vp, vp])},
+                    {"LOC_IBD_MAX_HAPS", "LOC_IBD_MAX_GAP", "LOC_IBD_PACK_COLS", "LOC_IBD_BLOCK"})
     assert (_abi.LOC_IBD_MAX_HAPS, _abi.LOC_IBD_MAX_GAP) == (IB.MAX_HAPS, IB.MAX_GAP) and IB.MAX_HAPS >= 32768 and IB.MAX_GAP == 8
-    lib = _lib.load()
-    for name in names:
-        fn = getattr(lib, name)
-        assert fn.restype is _abi.IBD_PROTOTYPES[name][0] and list(fn.argtypes) == _abi.IBD_PROTOTYPES[name][1]
 
 
 def test_paint_keeps_its_names_for_what_moved():

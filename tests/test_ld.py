@@ -5,7 +5,6 @@ and float64 from two products and one division of exact integers."""
 import ctypes as C
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -133,25 +132,14 @@ def test_lag_buckets():
 
 
 # ------------------------------------------------------------------ the binding
-def test_ld_header_is_bound_as_the_other_headers_are(repo_root):
-    from locator_amd import _abi, _lib
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(repo_root, "include", "locator_hip_ld.h")).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(loc_[a-z0-9_]+)\s*\(", src)))
-    assert names == ["loc_ld_band"] == sorted(_abi.LD_PROTOTYPES)
-    assert _lib.LD_SIGNATURES is _abi.LD_PROTOTYPES
-    others = (set(_abi.PROTOTYPES) | set(_abi.EXT_PROTOTYPES) | set(_abi.REGION_PROTOTYPES) | set(_abi.NEIGHBOR_PROTOTYPES)
-              | set(_abi.PCA_PROTOTYPES))
-    assert not set(names) & others
+def test_ld_header_is_bound_as_the_other_headers_are():
+    from locator_amd import _abi
+    from tests.abi_util import check_extension
     vp, i64 = C.c_void_p, C.c_int64
-    assert _abi.LD_PROTOTYPES["loc_ld_band"] == (C.c_int, [vp, i64, C.c_int, i64, C.c_int, vp, C.c_double, vp, vp, vp, vp])
-    assert set(_abi.LD_CONSTANTS) == {"LOC_LD_TILE", "LOC_LD_BLOCK", "LOC_LD_MAX_WINDOW"}
-    assert all(isinstance(v, int) and v > 0 for v in _abi.LD_CONSTANTS.values())
+    check_extension("ld", {"loc_ld_band": (C.c_int, [vp, i64, C.c_int, i64, C.c_int, vp, C.c_double, vp, vp, vp, vp])},
+                    {"LOC_LD_TILE", "LOC_LD_BLOCK", "LOC_LD_MAX_WINDOW"})
     assert (_abi.LOC_LD_TILE, _abi.LOC_LD_BLOCK, _abi.LOC_LD_MAX_WINDOW) == (LD.TILE, LD.BLOCK, LD.MAX_WINDOW)
     assert LD.TILE % 32 == 0 and LD.BLOCK % 32 == 0 and LD.MAX_WINDOW >= 512
-    assert not set(_abi.LD_CONSTANTS) & (set(_abi.CONSTANTS) | set(_abi.REGION_CONSTANTS) | set(_abi.NEIGHBOR_CONSTANTS)
-                                         | set(_abi.PCA_CONSTANTS))
-    fn = getattr(_lib.load(), "loc_ld_band")
-    assert fn.restype is C.c_int and list(fn.argtypes) == _abi.LD_PROTOTYPES["loc_ld_band"][1]
 
 
 def test_count_matrix_sites_is_the_count_matrix_not_transposed():

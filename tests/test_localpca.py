@@ -4,28 +4,21 @@ twelve follow y where the others follow x."""
 import ctypes as C
 import json
 import os
-import re
 
 import numpy as np
 import pytest
 
-from locator_amd import _abi
 from locator_amd import localpca as L
 from locator_amd import pca as P
 from tests import localpca_util as LU
 from tests import pca_util as U
 
 
-def test_the_binding_comes_from_the_header(repo_root):
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(repo_root, "include", "locator_hip_localpca.h")).read(), flags=re.S)
-    assert re.findall(r"\b(loc_\w+)\s*\(", src) == ["loc_grm_windows"] == sorted(_abi.LOCALPCA_PROTOTYPES)
+def test_the_binding_comes_from_the_header():
+    from tests.abi_util import check_extension
     i, i64, vp = C.c_int, C.c_int64, C.c_void_p
-    assert _abi.LOCALPCA_PROTOTYPES["loc_grm_windows"] == (i, [vp, i, i64, i64, vp, vp, vp, i, vp, vp])
-    assert _abi.LOCALPCA_CONSTANTS == {"LOC_LOCALPCA_MAX_WINDOWS": 65535} and L.MAX_WINDOWS == 65535
-    from locator_amd import _lib
-    assert _lib.LOCALPCA_SIGNATURES is _abi.LOCALPCA_PROTOTYPES
-    fn = _lib.load().loc_grm_windows
-    assert fn.restype is i and list(fn.argtypes) == _abi.LOCALPCA_PROTOTYPES["loc_grm_windows"][1]
+    check_extension("localpca", {"loc_grm_windows": (i, [vp, i, i64, i64, vp, vp, vp, i, vp, vp])}, {"LOC_LOCALPCA_MAX_WINDOWS": 65535})
+    assert L.MAX_WINDOWS == 65535
 
 
 # ------------------------------------------------------------------ windows

@@ -5,7 +5,6 @@ integers, and float64 from one division."""
 import ctypes as C
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -152,24 +151,15 @@ def test_longlat_errors_are_the_haversine_of_plot():
 
 
 # ------------------------------------------------------------------ the binding
-def test_neighbor_header_is_bound_as_the_other_headers_are(repo_root):
-    from locator_amd import _abi, _lib
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(repo_root, "include", "locator_hip_neighbors.h")).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(loc_[a-z0-9_]+)\s*\(", src)))
-    assert names == ["loc_ibs_knn", "loc_ibs_pairs", "loc_ibs_work_bytes"] == sorted(_abi.NEIGHBOR_PROTOTYPES)
-    assert _lib.NEIGHBOR_SIGNATURES is _abi.NEIGHBOR_PROTOTYPES
-    assert not set(names) & (set(_abi.PROTOTYPES) | set(_abi.EXT_PROTOTYPES) | set(_abi.REGION_PROTOTYPES))
+def test_neighbor_header_is_bound_as_the_other_headers_are():
+    from locator_amd import _abi
+    from tests.abi_util import check_extension
     vp, i64 = C.c_void_p, C.c_int64
-    assert _abi.NEIGHBOR_PROTOTYPES["loc_ibs_pairs"] == (C.c_int, [vp, C.c_int, i64, i64, C.c_int, vp, vp, vp, i64, vp])
-    assert _abi.NEIGHBOR_PROTOTYPES["loc_ibs_work_bytes"] == (i64, [C.c_int, i64, C.c_int])
-    assert _abi.NEIGHBOR_PROTOTYPES["loc_ibs_knn"] == (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp])
-    assert _abi.NEIGHBOR_CONSTANTS == {"LOC_IBS_TILE": 128, "LOC_IBS_BLOCK": 64}
+    check_extension("neighbor", {"loc_ibs_pairs": (C.c_int, [vp, C.c_int, i64, i64, C.c_int, vp, vp, vp, i64, vp]),
+                                 "loc_ibs_work_bytes": (i64, [C.c_int, i64, C.c_int]),
+                                 "loc_ibs_knn": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp])},
+                    {"LOC_IBS_TILE": 128, "LOC_IBS_BLOCK": 64})
     assert (_abi.LOC_IBS_TILE, _abi.LOC_IBS_BLOCK) == (NB.TILE, NB.BLOCK) == (128, 64)
-    assert not set(_abi.NEIGHBOR_CONSTANTS) & (set(_abi.CONSTANTS) | set(_abi.REGION_CONSTANTS))
-    lib = _lib.load()
-    for name in names:
-        fn = getattr(lib, name)
-        assert fn.restype is _abi.NEIGHBOR_PROTOTYPES[name][0] and list(fn.argtypes) == _abi.NEIGHBOR_PROTOTYPES[name][1]
 
 
 # ------------------------------------------------------------------ the command

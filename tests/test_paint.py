@@ -4,7 +4,6 @@ linkage, the split at a certain switch, the stretch without a switch in float32)
 import ctypes as C
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -15,25 +14,14 @@ from tests import paint_util as U
 
 
 # ------------------------------------------------------------------ the binding
-def test_paint_header_is_bound_as_the_other_headers_are(repo_root):
-    from locator_amd import _abi, _lib
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(repo_root, "include", "locator_hip_paint.h")).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(loc_[a-z0-9_]+)\s*\(", src)))
-    assert names == ["loc_paint_copy", "loc_paint_work_bytes"] == sorted(_abi.PAINT_PROTOTYPES)
-    assert _lib.PAINT_SIGNATURES is _abi.PAINT_PROTOTYPES
-    others = (set(_abi.PROTOTYPES) | set(_abi.EXT_PROTOTYPES) | set(_abi.REGION_PROTOTYPES) | set(_abi.NEIGHBOR_PROTOTYPES)
-              | set(_abi.PCA_PROTOTYPES) | set(_abi.LD_PROTOTYPES) | set(_abi.SPA_PROTOTYPES) | set(_abi.ADMIX_PROTOTYPES)
-              | set(_abi.LOCALPCA_PROTOTYPES))
-    assert not set(names) & others
+def test_paint_header_is_bound_as_the_other_headers_are():
+    from locator_amd import _abi
+    from tests.abi_util import check_extension
     vp, i64, i, f = C.c_void_p, C.c_int64, C.c_int, C.c_float
-    assert _abi.PAINT_PROTOTYPES["loc_paint_work_bytes"] == (i64, [i, i64, i, i])
-    assert _abi.PAINT_PROTOTYPES["loc_paint_copy"] == (i, [vp, i, i64, i64, vp, vp, vp, i, vp, f, i, vp, vp, vp, vp, vp, i64, vp])
-    assert set(_abi.PAINT_CONSTANTS) == {"LOC_PAINT_MAX_HAPS", "LOC_PAINT_LANE_COLS", "LOC_PAINT_LL_RUN", "LOC_PAINT_C_SLOTS"}
+    check_extension("paint", {"loc_paint_work_bytes": (i64, [i, i64, i, i]),
+                              "loc_paint_copy": (i, [vp, i, i64, i64, vp, vp, vp, i, vp, f, i, vp, vp, vp, vp, vp, i64, vp])},
+                    {"LOC_PAINT_MAX_HAPS", "LOC_PAINT_LANE_COLS", "LOC_PAINT_LL_RUN", "LOC_PAINT_C_SLOTS"})
     assert (_abi.LOC_PAINT_MAX_HAPS, _abi.LOC_PAINT_LANE_COLS) == (PT.MAX_HAPS, 4) == (4096, 4)
-    lib = _lib.load()
-    for name in names:
-        fn = getattr(lib, name)
-        assert fn.restype is _abi.PAINT_PROTOTYPES[name][0] and list(fn.argtypes) == _abi.PAINT_PROTOTYPES[name][1]
 
 
 # ------------------------------------------------------------------ copy_host

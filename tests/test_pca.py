@@ -4,7 +4,6 @@ include/locator_hip_pca.h, the --host command on the golden VCF, and the refusal
 import ctypes as C
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -112,25 +111,14 @@ def test_pc_r2_names_the_axis():
 
 
 # ------------------------------------------------------------------ the binding
-def test_pca_header_is_bound_as_the_other_headers_are(repo_root):
-    from locator_amd import _abi, _lib
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(repo_root, "include", "locator_hip_pca.h")).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(loc_[a-z0-9_]+)\s*\(", src)))
-    assert names == ["loc_grm_pairs", "loc_grm_work_bytes", "loc_pca_loadings"] == sorted(_abi.PCA_PROTOTYPES)
-    assert _lib.PCA_SIGNATURES is _abi.PCA_PROTOTYPES
-    assert not set(names) & (set(_abi.PROTOTYPES) | set(_abi.EXT_PROTOTYPES) | set(_abi.REGION_PROTOTYPES)
-                             | set(_abi.NEIGHBOR_PROTOTYPES))
+def test_pca_header_is_bound_as_the_other_headers_are():
+    from tests.abi_util import check_extension
     vp, i64 = C.c_void_p, C.c_int64
-    assert _abi.PCA_PROTOTYPES["loc_grm_pairs"] == (C.c_int, [vp, C.c_int, i64, i64, vp, vp, C.c_int, vp, vp, i64, vp])
-    assert _abi.PCA_PROTOTYPES["loc_grm_work_bytes"] == (i64, [C.c_int, i64, C.c_int])
-    assert _abi.PCA_PROTOTYPES["loc_pca_loadings"] == (C.c_int, [vp, C.c_int, i64, i64, vp, vp, vp, C.c_int, vp, vp])
-    assert _abi.PCA_CONSTANTS == {"LOC_PCA_TILE": 128, "LOC_PCA_BLOCK": 32, "LOC_PCA_MAX_NPC": 64, "LOC_PCA_SITES": 256}
+    check_extension("pca", {"loc_grm_pairs": (C.c_int, [vp, C.c_int, i64, i64, vp, vp, C.c_int, vp, vp, i64, vp]),
+                            "loc_grm_work_bytes": (i64, [C.c_int, i64, C.c_int]),
+                            "loc_pca_loadings": (C.c_int, [vp, C.c_int, i64, i64, vp, vp, vp, C.c_int, vp, vp])},
+                    {"LOC_PCA_TILE": 128, "LOC_PCA_BLOCK": 32, "LOC_PCA_MAX_NPC": 64, "LOC_PCA_SITES": 256})
     assert (P.TILE, P.BLOCK, P.NPC_LIMIT) == (128, 32, 64)
-    assert not set(_abi.PCA_CONSTANTS) & (set(_abi.CONSTANTS) | set(_abi.REGION_CONSTANTS) | set(_abi.NEIGHBOR_CONSTANTS))
-    lib = _lib.load()
-    for name in names:
-        fn = getattr(lib, name)
-        assert fn.restype is _abi.PCA_PROTOTYPES[name][0] and list(fn.argtypes) == _abi.PCA_PROTOTYPES[name][1]
 
 
 # ------------------------------------------------------------------ the command

@@ -53,22 +53,16 @@ def no_device(monkeypatch):
 
 
 # ------------------------------------------------------------------ the entry point's declaration and binding
-def test_extension_header_is_bound_as_the_main_header_is(repo_root):
+def test_extension_header_is_bound_as_the_main_header_is():
     """include/locator_hip_query.h (entry points after version 1 of the ABI, whose list tests/test_abi.py pins): every
     function it declares is exported by the library and bound from its prototype, by the parser that reads locator_hip.h."""
     import ctypes as C
-    import re
 
-    from locator_amd import _abi, _lib
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(repo_root, "include", "locator_hip_query.h")).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(loc_[a-z0-9_]+)\s*\(", src)))
-    assert names == ["loc_query_rows_dosage"] == sorted(_lib.EXT_SIGNATURES) and _lib.EXT_SIGNATURES is _abi.EXT_PROTOTYPES
-    assert not set(names) & set(_lib.SIGNATURES)
+    from locator_amd import _abi
+    from tests.abi_util import check_extension
     vp = C.c_void_p
-    assert _abi.EXT_PROTOTYPES["loc_query_rows_dosage"] == (
-        C.c_int, [vp, C.c_int64, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int64, vp])
-    fn = _lib.load().loc_query_rows_dosage
-    assert fn.restype is C.c_int and list(fn.argtypes) == _abi.EXT_PROTOTYPES["loc_query_rows_dosage"][1]
+    check_extension("ext", {"loc_query_rows_dosage": (C.c_int, [vp, C.c_int64, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int64, vp])},
+                    {})
     with pytest.raises(ValueError):
         _abi.parse("int loc_f(size_t n);")                       # the same refusals as for the main header
 

@@ -3,7 +3,6 @@ tests/test_gpu_regions.py - on hand-written cases and against matplotlib's point
 search, the tables, the stops, and the binding of include/locator_hip_regions.h.  Nothing here needs a GPU."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -324,20 +323,11 @@ def test_exactly_one_of_map_and_regions(tmp_path, capsys):
 
 
 # ------------------------------------------------------------------ the binding
-def test_region_header_is_bound_as_the_other_headers_are(repo_root):
-    from locator_amd import _abi, _lib
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(repo_root, "include", "locator_hip_regions.h")).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(loc_[a-z0-9_]+)\s*\(", src)))
-    assert names == ["loc_region_assign", "loc_region_nearest"] == sorted(_abi.REGION_PROTOTYPES)
-    assert _lib.REGION_SIGNATURES is _abi.REGION_PROTOTYPES
-    assert not set(names) & (set(_abi.PROTOTYPES) | set(_abi.EXT_PROTOTYPES))
+def test_region_header_is_bound_as_the_other_headers_are():
+    from locator_amd import _abi
+    from tests.abi_util import check_extension
     vp = C.c_void_p
-    assert _abi.REGION_PROTOTYPES["loc_region_assign"] == (C.c_int, [vp, C.c_int64, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp])
-    assert _abi.REGION_PROTOTYPES["loc_region_nearest"] == (C.c_int, [vp, C.c_int64, vp, C.c_int64, vp, vp, vp])
-    assert _abi.REGION_CONSTANTS == {"LOC_REGION_TILE": 256, "LOC_REGION_STAGE": 2048}
+    check_extension("region", {"loc_region_assign": (C.c_int, [vp, C.c_int64, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]),
+                               "loc_region_nearest": (C.c_int, [vp, C.c_int64, vp, C.c_int64, vp, vp, vp])},
+                    {"LOC_REGION_TILE": 256, "LOC_REGION_STAGE": 2048})
     assert (_abi.LOC_REGION_TILE, _abi.LOC_REGION_STAGE) == (R.TILE, R.STAGE) == (256, 2048)
-    assert not set(_abi.REGION_CONSTANTS) & set(_abi.CONSTANTS)
-    lib = _lib.load()
-    for n in names:
-        fn = getattr(lib, n)
-        assert fn.restype is C.c_int and list(fn.argtypes) == _abi.REGION_PROTOTYPES[n][1]

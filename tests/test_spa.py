@@ -5,7 +5,6 @@ import ctypes as C
 import hashlib
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -18,32 +17,19 @@ from tests import spa_util as U
 
 
 # ------------------------------------------------------------------ the binding
-def test_spa_header_is_bound_as_the_other_headers_are(repo_root):
-    from locator_amd import _abi, _lib
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(repo_root, "include", "locator_hip_spa.h")).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(loc_[a-z0-9_]+)\s*\(", src)))
-    assert names == ["loc_spa_fit", "loc_spa_grid", "loc_spa_grid_work_bytes"] == sorted(_abi.SPA_PROTOTYPES)
-    assert _lib.SPA_SIGNATURES is _abi.SPA_PROTOTYPES
-    others = (set(_abi.PROTOTYPES) | set(_abi.EXT_PROTOTYPES) | set(_abi.REGION_PROTOTYPES) | set(_abi.NEIGHBOR_PROTOTYPES)
-              | set(_abi.PCA_PROTOTYPES) | set(_abi.LD_PROTOTYPES))
-    assert not set(names) & others
+def test_spa_header_is_bound_as_the_other_headers_are():
+    from locator_amd import _abi
+    from tests.abi_util import check_extension
     vp, i64, i = C.c_void_p, C.c_int64, C.c_int
-    assert _abi.SPA_PROTOTYPES["loc_spa_fit"] == (i, [vp, i64, i, i64, i, vp, vp, C.c_float, i, vp, vp, vp])
-    assert _abi.SPA_PROTOTYPES["loc_spa_grid_work_bytes"] == (i64, [i, i64, i, i])
-    assert _abi.SPA_PROTOTYPES["loc_spa_grid"] == (i, [vp, i, i64, i64, i, vp, vp, vp, vp, i, i, vp, vp, i64, vp])
-    assert set(_abi.SPA_CONSTANTS) == {"LOC_SPA_TILE", "LOC_SPA_BLOCK", "LOC_SPA_MAX_STEP", "LOC_SPA_MAX_ITERS", "LOC_SPA_MAX_NODES",
-                                       "LOC_SPA_FIT_SITES", "LOC_SPA_FIT_CHUNK", "LOC_SPA_TILE_SAMPLES"}
-    assert all(isinstance(v, int) and v > 0 for v in _abi.SPA_CONSTANTS.values())
+    check_extension("spa", {"loc_spa_fit": (i, [vp, i64, i, i64, i, vp, vp, C.c_float, i, vp, vp, vp]),
+                            "loc_spa_grid_work_bytes": (i64, [i, i64, i, i]),
+                            "loc_spa_grid": (i, [vp, i, i64, i64, i, vp, vp, vp, vp, i, i, vp, vp, i64, vp])},
+                    {"LOC_SPA_TILE", "LOC_SPA_BLOCK", "LOC_SPA_MAX_STEP", "LOC_SPA_MAX_ITERS", "LOC_SPA_MAX_NODES",
+                     "LOC_SPA_FIT_SITES", "LOC_SPA_FIT_CHUNK", "LOC_SPA_TILE_SAMPLES"})
     assert (_abi.LOC_SPA_TILE, _abi.LOC_SPA_BLOCK, _abi.LOC_SPA_MAX_STEP, _abi.LOC_SPA_MAX_ITERS, _abi.LOC_SPA_MAX_NODES) == (
         S.TILE, S.BLOCK, S.MAX_STEP, S.MAX_ITERS, S.MAX_NODES) == (128, 32, 2, 64, 128 * 128)
     assert _abi.LOC_SPA_TILE_SAMPLES == S.TILE_SAMPLES == 256
     assert S.GRID_RANGE[1] ** 2 == S.MAX_NODES
-    assert not set(_abi.SPA_CONSTANTS) & (set(_abi.CONSTANTS) | set(_abi.REGION_CONSTANTS) | set(_abi.NEIGHBOR_CONSTANTS)
-                                          | set(_abi.PCA_CONSTANTS) | set(_abi.LD_CONSTANTS))
-    lib = _lib.load()
-    for name in names:
-        fn = getattr(lib, name)
-        assert fn.restype is _abi.SPA_PROTOTYPES[name][0] and list(fn.argtypes) == _abi.SPA_PROTOTYPES[name][1]
 
 
 # ------------------------------------------------------------------ fit_host

@@ -185,7 +185,7 @@ def main():
     alt = None
     if a.alt_lib is not None:
         alt = C.CDLL(os.path.abspath(a.alt_lib))
-        alt.loc_grm_windows.restype, alt.loc_grm_windows.argtypes = _abi.LOCALPCA_PROTOTYPES["loc_grm_windows"]
+        alt.loc_grm_windows.restype, alt.loc_grm_windows.argtypes = _abi.ALL_PROTOTYPES["loc_grm_windows"]
     rng = np.random.default_rng(a.seed)
     runs = []
     for shape in a.shapes:

@@ -50,7 +50,7 @@ def planted(N, K, rng, founders=8, stay=0.98, width=0.12, flips=0.01, missing=0.
 
 def bind(path):
     lib = C.CDLL(path)
-    for name, (res, args) in _abi.PAINT_PROTOTYPES.items():
+    for name, (res, args) in _abi.EXTENSIONS["paint"].prototypes.items():
         getattr(lib, name).restype, getattr(lib, name).argtypes = res, args
     return lib
 
