@@ -106,7 +106,9 @@ def emissions(h, j, rcols, dn, theta, dtype):
     return np.where(dn, e, f(0)).astype(dtype)
 
 
-def _copy_batch(h, dn, rcols, rho, theta, dtype):
+def forward_batch(h, dn, rcols, rho, theta, dtype):
+    """The forward pass of the module text for the recipient columns rcols with the donor flags dn [R][H]: (u [R][1], rho with
+    rho[0] = 1 in dtype, a-hat [K][R][H], c [K][R], ll [R] float64).  copy_host and impute.dose_host walk back from it."""
     f = np.dtype(dtype).type
     K, (R, H) = h.shape[0], dn.shape
     u = (f(1) / dn.sum(axis=1).astype(dtype))[:, None]
@@ -119,6 +121,13 @@ def _copy_batch(h, dn, rcols, rho, theta, dtype):
         ah = a * (f(1) / c)[:, None]
         ah_all[j], c_all[j] = ah, c
         ll += np.log(c.astype(np.float64))
+    return u, rj, ah_all, c_all, ll
+
+
+def _copy_batch(h, dn, rcols, rho, theta, dtype):
+    f = np.dtype(dtype).type
+    K, (R, H) = h.shape[0], dn.shape
+    u, rj, ah_all, c_all, ll = forward_batch(h, dn, rcols, rho, theta, dtype)
     b = np.broadcast_to(u, (R, H)).astype(dtype)
     sa, ca = np.zeros((R, H), dtype=dtype), np.zeros((R, H), dtype=dtype)
     tiny = np.finfo(dtype).tiny
@@ -283,6 +292,24 @@ def sample_weights(copy, hap, donor_samples, rho, theta, max_haps=MAX_HAPS, reci
     return W, C, ll, nd, len(groups)
 
 
+def estimate_switch(copy, hap, donors, g, first, switch, em_rounds, em_sample, theta, max_haps=MAX_HAPS, pool=None):
+    """(lambda, history [(round, lambda, sum of ll)], the recipient samples of the rounds): the module text's estimate of the
+    switch rate from the first value `switch`.  pool: the samples the recipients are spread over evenly (default all)."""
+    pool = np.arange(hap.shape[1] // 2) if pool is None else np.asarray(pool, dtype=np.int64)
+    m = min(em_sample, len(pool))
+    em_recipients = pool[np.unique((np.arange(m) * len(pool)) // max(m, 1))]
+    history, lam = [], float(switch)
+    for t in range(em_rounds):
+        rho = switch_rates(lam, g, first)
+        _, C, ll, nd, _ = sample_weights(copy, hap, donors, rho, theta, max_haps, em_recipients)
+        history.append((t, lam, float(ll.sum())))
+        # C holds the chunks of the recipients that ran, folded over haplotypes: its sum is theirs
+        lam = em_update(lam, rho, C, nd)
+    if history:
+        lam = max(history, key=lambda r: (r[2], -r[0]))[1]
+    return lam, history, em_recipients
+
+
 # the placement from a sample-by-sample weight is shared with the ibd command: baselines.py holds it, these are its names here
 top_donors, placements = B.top_donors, B.placements
 
@@ -333,17 +360,7 @@ def paint(hap, c, P, samples, locs, chrom=None, pos=None, out=None, switch=0.01,
         copy = lambda *six: copy_device(*six, budget=budget, device=device)
     g, first = site_gaps(chrom, pos, K, uniform)
 
-    m = min(em_sample, N)
-    em_recipients = np.unique((np.arange(m) * N) // m)
-    history, lam = [], float(switch)
-    for t in range(em_rounds):
-        rho = switch_rates(lam, g, first)
-        _, C, ll, nd, _ = sample_weights(copy, hap, donors, rho, theta, max_haps, em_recipients)
-        history.append((t, lam, float(ll.sum())))
-        # C holds the chunks of the recipients that ran, folded over haplotypes: its sum is theirs
-        lam = em_update(lam, rho, C, nd)
-    if history:
-        lam = max(history, key=lambda r: (r[2], -r[0]))[1]
+    lam, history, em_recipients = estimate_switch(copy, hap, donors, g, first, switch, em_rounds, em_sample, theta, max_haps)
     rho = switch_rates(lam, g, first)
     W, C, ll, nd, n_groups = sample_weights(copy, hap, donors, rho, theta, max_haps)
 
