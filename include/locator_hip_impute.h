@@ -1,7 +1,7 @@
 /* Entry point of liblocator_hip.so behind `python -m locator_amd.impute` (locator_amd/csrc/impute_kernels.hip): the allele
  * dosage of every site of a recipient haplotype under the copying model of locator_hip_paint.h.  The spelling rules of
  * locator_hip.h hold (one declaration per `;`, comments only as this one), and locator_amd/_abi.py derives the ctypes binding
- * from this file with the same reader (LATER["impute"], and the LOC_IMPUTE_* constants).  As in locator_hip.h: device pointers
+ * from this file with the same reader (EXTENSIONS["impute"], and the LOC_IMPUTE_* constants).  As in locator_hip.h: device pointers
  * unless named h_*, `stream` a hipStream_t, 0 = success, -1 = bad arguments with loc_last_error set and nothing launched.  The
  * NumPy definition is locator_amd/impute.py: dose_host. */
 #ifndef LOCATOR_HIP_IMPUTE_H

@@ -125,49 +125,17 @@ __global__ __launch_bounds__(64) void impute_kernel(const int8_t* __restrict__ h
 }
 
 // ---------------------------------------------------------------------------------------------------------------- launcher
-template <int NR>
-static int ik_launch(const int8_t* h, int H, int64_t K, int64_t pitch, const uint8_t* donor, const int32_t* owner, const int32_t* rec,
-                     int R, const float* rho, float theta, const pk_layout& L, float* dose, double* ll, int32_t* n_donors, float* work,
-                     hipStream_t stream) {
-    hipLaunchKernelGGL(impute_kernel<NR>, dim3((unsigned)R), dim3(64), 0, stream, h, H, K, pitch, donor, owner, rec, rho, theta, L.B, dose,
-                       ll, n_donors, work, L.per_rec);
-    LOC_CHECK_LAUNCH();
-    return 0;
-}
-
 extern "C" int loc_impute_dose(const int8_t* h, int H, int64_t K, int64_t pitch, const uint8_t* donor, const int32_t* owner,
                                const int32_t* rec, int R, const float* rho, float theta, int block, float* dose, double* ll,
                                int32_t* n_donors, void* work, int64_t work_bytes, void* stream) {
-    if (!pk_args_ok("loc_impute_dose", H, K, R, block, pitch, work_bytes, theta)) return -1;
-    if (R == 0) return 0;
-    if (!dose || !ll || !n_donors || !rec || !donor || !owner || (K > 0 && (!h || !rho))) {
-        loc_set_error("loc_impute_dose: null buffer");
-        return -1;
-    }
-    if ((uintptr_t)dose % 4 != 0 || (uintptr_t)ll % 8 != 0 || (uintptr_t)n_donors % 4 != 0 || (uintptr_t)rho % 4 != 0 ||
-        (uintptr_t)owner % 4 != 0 || (uintptr_t)rec % 4 != 0) {
-        loc_set_error("loc_impute_dose: dose, n_donors, rho, owner and rec must be multiples of 4 bytes, ll of 8");
-        return -1;
-    }
-    if (K > 0 && !pt_rows_aligned("loc_impute_dose", h, pitch)) return -1;
-    const pk_layout L = pk_work(H, K, R, block);
-    if (!pt_work_ok("loc_impute_dose", "loc_paint_work_bytes", work, work_bytes, L.bytes)) return -1;
-    hipStream_t s = (hipStream_t)stream;
-    if (const int bad = pk_rec_ok("loc_impute_dose", rec, R, H, s)) return bad;
-    if (K == 0) {
-        hipError_t e = hipMemsetAsync(ll, 0, (size_t)R * sizeof(double), s);
-        if (e == hipSuccess) e = hipMemsetAsync(n_donors, 0, (size_t)R * sizeof(int32_t), s);
-        if (e != hipSuccess) {
-            loc_set_error("loc_impute_dose: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-        return 0;
-    }
-    switch (pk_sweeps(H)) {
-        case 1: return ik_launch<1>(h, H, K, pitch, donor, owner, rec, R, rho, theta, L, dose, ll, n_donors, (float*)work, s);
-        case 2: return ik_launch<2>(h, H, K, pitch, donor, owner, rec, R, rho, theta, L, dose, ll, n_donors, (float*)work, s);
-        case 4: return ik_launch<4>(h, H, K, pitch, donor, owner, rec, R, rho, theta, L, dose, ll, n_donors, (float*)work, s);
-        case 8: return ik_launch<8>(h, H, K, pitch, donor, owner, rec, R, rho, theta, L, dose, ll, n_donors, (float*)work, s);
-        default: return ik_launch<16>(h, H, K, pitch, donor, owner, rec, R, rho, theta, L, dose, ll, n_donors, (float*)work, s);
-    }
+    const pk_call c = {h, H, K, pitch, donor, owner, rec, R, rho, theta, block, ll, n_donors, work, work_bytes, (hipStream_t)stream};
+    const pk_out outs[] = {{"dose", dose, 0}};
+    pk_layout L;
+    int rc;
+    if (!pk_enter("loc_impute_dose", c, outs, 1, L, rc)) return rc;
+    pk_dispatch(H, [&](auto nr) {
+        hipLaunchKernelGGL(impute_kernel<decltype(nr)::value>, dim3((unsigned)R), dim3(64), 0, c.stream, h, H, K, pitch, donor, owner, rec,
+                           rho, theta, L.B, dose, ll, n_donors, (float*)work, L.per_rec);
+    });
+    return pk_launched("ik_launch");                          // the name this message has carried since the first launcher
 }

@@ -14,6 +14,8 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
+#include <string>
+#include <type_traits>
 #include <vector>
 
 #pragma clang fp contract(off)
@@ -248,4 +250,77 @@ static int pk_rec_ok(const char* who, const int32_t* rec, int R, int H, hipStrea
             return -1;
         }
     return 0;
+}
+
+// What the two entry points take alike, and an output of a call's own: its name in the messages, where it is, and the bytes
+// that K = 0 zeroes (0: none).
+struct pk_call {
+    const int8_t* h; int H; int64_t K, pitch; const uint8_t* donor; const int32_t* owner; const int32_t* rec; int R;
+    const float* rho; float theta; int block; double* ll; int32_t* n_donors; void* work; int64_t work_bytes; hipStream_t stream;
+};
+struct pk_out { const char* name; void* p; size_t zero_bytes; };
+
+// Every step of an entry point before its launch, in the order the header states: the refusals, R = 0, the scratch layout into
+// L, rec read back, the zeros of K = 0.  true: launch.  false: the entry point returns rc (0: nothing left to do; -1 or the HIP
+// error: refused, loc_set_error called).
+static bool pk_enter(const char* who, const pk_call& c, const pk_out* outs, int n_outs, pk_layout& L, int& rc) {
+    rc = -1;
+    if (!pk_args_ok(who, c.H, c.K, c.R, c.block, c.pitch, c.work_bytes, c.theta)) return false;
+    if (c.R == 0) {
+        rc = 0;
+        return false;
+    }
+    bool null = !c.ll || !c.n_donors || !c.rec || !c.donor || !c.owner || (c.K > 0 && (!c.h || !c.rho));
+    bool odd = (uintptr_t)c.ll % 8 != 0 || (uintptr_t)c.n_donors % 4 != 0 || (uintptr_t)c.rho % 4 != 0 || (uintptr_t)c.owner % 4 != 0 ||
+               (uintptr_t)c.rec % 4 != 0;
+    std::string names;
+    for (int i = 0; i < n_outs; ++i) {
+        null = null || !outs[i].p;
+        odd = odd || (uintptr_t)outs[i].p % 4 != 0;
+        names += outs[i].name;
+        names += ", ";
+    }
+    if (null) {
+        loc_set_error("%s: null buffer", who);
+        return false;
+    }
+    if (odd) {
+        loc_set_error("%s: %sn_donors, rho, owner and rec must be multiples of 4 bytes, ll of 8", who, names.c_str());
+        return false;
+    }
+    if (c.K > 0 && !pt_rows_aligned(who, c.h, c.pitch)) return false;
+    L = pk_work(c.H, c.K, c.R, c.block);
+    if (!pt_work_ok(who, "loc_paint_work_bytes", c.work, c.work_bytes, L.bytes)) return false;
+    if ((rc = pk_rec_ok(who, c.rec, c.R, c.H, c.stream)) != 0) return false;
+    if (c.K > 0) return true;
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < n_outs && e == hipSuccess; ++i)
+        if (outs[i].zero_bytes) e = hipMemsetAsync(outs[i].p, 0, outs[i].zero_bytes, c.stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c.ll, 0, (size_t)c.R * sizeof(double), c.stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c.n_donors, 0, (size_t)c.R * sizeof(int32_t), c.stream);
+    if (e != hipSuccess) {
+        loc_set_error("%s: %s", who, hipGetErrorString(e));
+        rc = (int)e;
+    }
+    return false;
+}
+
+// f(std::integral_constant<int, NR>()) for the NR of H columns: the one switch over pk_sweeps
+template <class F>
+static void pk_dispatch(int H, F&& f) {
+    switch (pk_sweeps(H)) {
+        case 1: return f(std::integral_constant<int, 1>());
+        case 2: return f(std::integral_constant<int, 2>());
+        case 4: return f(std::integral_constant<int, 4>());
+        case 8: return f(std::integral_constant<int, 8>());
+        default: return f(std::integral_constant<int, 16>());
+    }
+}
+
+// after pk_dispatch: 0, or the HIP error of the launch under the name `who`
+static int pk_launched(const char* who) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return 0;
+    loc_set_error("%s: %s", who, hipGetErrorString(e));
+    return (int)e;
 }

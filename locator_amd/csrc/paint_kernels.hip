@@ -167,52 +167,18 @@ extern "C" int64_t loc_paint_work_bytes(int H, int64_t K, int R, int block) {
     return pk_work(H, K, R, block).bytes;
 }
 
-template <int NR>
-static int pk_launch(const int8_t* h, int H, int64_t K, int64_t pitch, const uint8_t* donor, const int32_t* owner, const int32_t* rec,
-                     int R, const float* rho, float theta, const pk_layout& L, float* share, float* chunks, double* ll,
-                     int32_t* n_donors, float* work, hipStream_t stream) {
-    hipLaunchKernelGGL(paint_kernel<NR>, dim3((unsigned)R), dim3(64), 0, stream, h, H, K, pitch, donor, owner, rec, rho, theta, L.B, share,
-                       chunks, ll, n_donors, work, L.per_rec);
-    LOC_CHECK_LAUNCH();
-    return 0;
-}
-
 extern "C" int loc_paint_copy(const int8_t* h, int H, int64_t K, int64_t pitch, const uint8_t* donor, const int32_t* owner,
                               const int32_t* rec, int R, const float* rho, float theta, int block, float* share, float* chunks,
                               double* ll, int32_t* n_donors, void* work, int64_t work_bytes, void* stream) {
-    if (!pk_args_ok("loc_paint_copy", H, K, R, block, pitch, work_bytes, theta)) return -1;
-    if (R == 0) return 0;
-    if (!share || !chunks || !ll || !n_donors || !rec || !donor || !owner || (K > 0 && (!h || !rho))) {
-        loc_set_error("loc_paint_copy: null buffer");
-        return -1;
-    }
-    if ((uintptr_t)share % 4 != 0 || (uintptr_t)chunks % 4 != 0 || (uintptr_t)ll % 8 != 0 || (uintptr_t)n_donors % 4 != 0 ||
-        (uintptr_t)rho % 4 != 0 || (uintptr_t)owner % 4 != 0 || (uintptr_t)rec % 4 != 0) {
-        loc_set_error("loc_paint_copy: share, chunks, n_donors, rho, owner and rec must be multiples of 4 bytes, ll of 8");
-        return -1;
-    }
-    if (K > 0 && !pt_rows_aligned("loc_paint_copy", h, pitch)) return -1;
-    const pk_layout L = pk_work(H, K, R, block);
-    if (!pt_work_ok("loc_paint_copy", "loc_paint_work_bytes", work, work_bytes, L.bytes)) return -1;
-    hipStream_t s = (hipStream_t)stream;
-    if (const int bad = pk_rec_ok("loc_paint_copy", rec, R, H, s)) return bad;
-    if (K == 0) {
-        const size_t n = (size_t)R * (size_t)H * sizeof(float);
-        hipError_t e = hipMemsetAsync(share, 0, n, s);
-        if (e == hipSuccess) e = hipMemsetAsync(chunks, 0, n, s);
-        if (e == hipSuccess) e = hipMemsetAsync(ll, 0, (size_t)R * sizeof(double), s);
-        if (e == hipSuccess) e = hipMemsetAsync(n_donors, 0, (size_t)R * sizeof(int32_t), s);
-        if (e != hipSuccess) {
-            loc_set_error("loc_paint_copy: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-        return 0;
-    }
-    switch (pk_sweeps(H)) {
-        case 1: return pk_launch<1>(h, H, K, pitch, donor, owner, rec, R, rho, theta, L, share, chunks, ll, n_donors, (float*)work, s);
-        case 2: return pk_launch<2>(h, H, K, pitch, donor, owner, rec, R, rho, theta, L, share, chunks, ll, n_donors, (float*)work, s);
-        case 4: return pk_launch<4>(h, H, K, pitch, donor, owner, rec, R, rho, theta, L, share, chunks, ll, n_donors, (float*)work, s);
-        case 8: return pk_launch<8>(h, H, K, pitch, donor, owner, rec, R, rho, theta, L, share, chunks, ll, n_donors, (float*)work, s);
-        default: return pk_launch<16>(h, H, K, pitch, donor, owner, rec, R, rho, theta, L, share, chunks, ll, n_donors, (float*)work, s);
-    }
+    const pk_call c = {h, H, K, pitch, donor, owner, rec, R, rho, theta, block, ll, n_donors, work, work_bytes, (hipStream_t)stream};
+    const size_t rows = (size_t)(R > 0 ? R : 0) * (size_t)H * sizeof(float);
+    const pk_out outs[] = {{"share", share, rows}, {"chunks", chunks, rows}};
+    pk_layout L;
+    int rc;
+    if (!pk_enter("loc_paint_copy", c, outs, 2, L, rc)) return rc;
+    pk_dispatch(H, [&](auto nr) {
+        hipLaunchKernelGGL(paint_kernel<decltype(nr)::value>, dim3((unsigned)R), dim3(64), 0, c.stream, h, H, K, pitch, donor, owner, rec,
+                           rho, theta, L.B, share, chunks, ll, n_donors, (float*)work, L.per_rec);
+    });
+    return pk_launched("pk_launch");                          // the name this message has carried since the first launcher
 }

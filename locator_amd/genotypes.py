@@ -595,6 +595,15 @@ def zarr_sites(callset):
     return out
 
 
+def site_columns(d):
+    """read_vcf(sites=True) / zarr_sites dict -> {chrom, pos, ref, alt}: ALT[0] of each variant."""
+    alt = np.asarray(d["variants/ALT"], dtype=object)
+    return {"chrom": np.asarray(d["variants/CHROM"], dtype=object).astype(str),
+            "pos": np.asarray(d["variants/POS"], dtype=np.int64),
+            "ref": np.asarray(d["variants/REF"], dtype=object).astype(str),
+            "alt": (alt[:, 0] if alt.ndim == 2 else alt).astype(str)}
+
+
 def matrix_sites(path):
     """The column names of a --matrix file after 'sampleID': the identities of its sites."""
     opener = gzip.open if str(path).endswith(".gz") else open

@@ -90,20 +90,7 @@ def _dose_batch(h, dn, rcols, rho, theta, dtype):
 
 def dose_host(h, donor, owner, rec, rho, theta, dtype=np.float64):
     """(dose [R][K] dtype, ll [R] float64, n_donors [R] int32): the definition in the module text."""
-    h, donor, owner, rec, rho = PT._check(h, donor, owner, rec, rho, theta)
-    K, H, R = h.shape[0], len(donor), len(rec)
-    dose = np.full((R, K), np.nan, dtype=dtype)
-    ll, n_donors = np.zeros(R), np.zeros(R, dtype=np.int32)
-    if K == 0 or R == 0:
-        return dose, ll, n_donors
-    dn = donor[None, :] & (owner[None, :] != owner[rec][:, None])
-    n_donors[:] = dn.sum(axis=1)
-    live = np.flatnonzero(n_donors > 0)
-    step = max(1, PT.HOST_BATCH_BYTES // (K * H * np.dtype(dtype).itemsize))
-    for a in range(0, len(live), step):
-        rows = live[a:a + step]
-        dose[rows], ll[rows] = _dose_batch(h, dn[rows], rec[rows], rho, theta, dtype)
-    return dose, ll, n_donors
+    return PT._host_model(_dose_batch, (("K", dtype, np.nan),), h, donor, owner, rec, rho, theta, dtype)
 
 
 # ---------------------------------------------------------------- the device form
@@ -111,38 +98,8 @@ def dose_host(h, donor, owner, rec, rho, theta, dtype=np.float64):
 def dose_device(h, donor, owner, rec, rho, theta, block=0, pitch=None, pad_fill=-1, fill=None, budget=4 << 30, device="cuda:0"):
     """dose_host's answer from loc_impute_dose launches (dose float32), the recipients in batches whose scratch and dose rows
     stay within `budget` bytes.  fill: a 32-bit pattern that scratch and the outputs hold before a launch (tests)."""
-    import torch as t
-    from . import _device as D, _lib
-    lib = _lib.load()
-    h, dflag, owner, rec, rho = PT._check(h, donor, owner, rec, rho, theta)
-    K, H, R = h.shape[0], len(dflag), len(rec)
-    buf = B.padded(np.ascontiguousarray(h[:, :H]), pitch, pad_fill)
-    with t.cuda.device(device):
-        d_h, d_donor, d_owner = D.put(buf, np.int8, device), D.put(dflag, np.uint8, device), D.put(owner, np.int32, device)
-        d_rho = D.put(rho if K else np.zeros(1), np.float32, device)
-        one = int(lib.loc_paint_work_bytes(H, K, 1, int(block)))
-        if one < 0:
-            _lib.check(-1, "loc_paint_work_bytes")
-        step = max(1, int(budget) // max(one + 4 * K, 1))
-        dose = np.full((R, K), np.nan, dtype=np.float32)
-        ll, n_donors = np.zeros(R), np.zeros(R, dtype=np.int32)
-        for a in range(0, R, step):
-            n = min(step, R - a)
-            d_rec = D.put(rec[a:a + n], np.int32, device)
-            d_dose = t.empty((n, max(K, 1)), dtype=t.float32, device=device)
-            d_ll = t.empty(n, dtype=t.float64, device=device)
-            d_nd = t.empty(n, dtype=t.int32, device=device)
-            d_work, work_bytes = D.work_buffer(lib, "loc_paint_work_bytes", H, K, n, int(block), device=device, fill=fill)
-            D.prefill((d_dose, d_ll, d_nd), fill)
-            _lib.check(lib.loc_impute_dose(d_h.data_ptr(), H, K, int(buf.shape[1]), d_donor.data_ptr(), d_owner.data_ptr(),
-                                           d_rec.data_ptr(), n, d_rho.data_ptr(), float(theta), int(block), d_dose.data_ptr(),
-                                           d_ll.data_ptr(), d_nd.data_ptr(), d_work.data_ptr(), work_bytes, D.stream()),
-                       "loc_impute_dose")
-            if K:
-                dose[a:a + n] = d_dose.cpu().numpy()
-            ll[a:a + n], n_donors[a:a + n] = d_ll.cpu().numpy(), d_nd.cpu().numpy()
-            del d_work
-    return dose, ll, n_donors
+    return PT._device_model("loc_impute_dose", (("K", np.float32, np.nan),), 4, h, donor, owner, rec, rho, theta, block, pitch, pad_fill,
+                            fill, budget, device)
 
 
 # ---------------------------------------------------------------- the command's pieces
@@ -166,10 +123,7 @@ def read_phased(path, zarr):
     if gt.ndim != 3 or gt.shape[2] != 2:
         raise SystemExit(f"{PROG}: {path}: calls of ploidy {gt.shape[2] if gt.ndim == 3 else '?'}: the copying model is built for two "
                          "haplotypes a sample")
-    alt = np.asarray(d["variants/ALT"], dtype=object)
-    return {"gt": gt, "samples": np.asarray(d["samples"]).astype(str), "chrom": np.asarray(d["variants/CHROM"]).astype(str),
-            "pos": np.asarray(d["variants/POS"], dtype=np.int64), "ref": np.asarray(d["variants/REF"]).astype(str),
-            "alt": (alt[:, 0] if alt.ndim == 2 else alt).astype(str)}
+    return {"gt": gt, "samples": np.asarray(d["samples"]).astype(str), **G.site_columns(d)}
 
 
 def biallelic(d):
@@ -207,25 +161,19 @@ def run_model(dose, hap, donor_samples, want, rho, theta, max_haps=MAX_HAPS):
     """The model over paint's launch groups for the haplotype columns flagged in want [2 M]: (their columns ascending, dose
     [R][K], ll [R], n_donors [R], number of groups).  dose: dose_host or dose_device with the leading six arguments."""
     M = hap.shape[1] // 2
-    groups = PT.launch_groups(M, donor_samples, max_haps)
-    cols_of, parts = [], []
-    for cols, recs in groups:
-        hcols = np.stack([2 * cols, 2 * cols + 1], axis=1).reshape(-1)
-        at = np.flatnonzero(np.isin(cols, recs))
-        rec = np.stack([2 * at, 2 * at + 1], axis=1).reshape(-1)
+    n_groups, cols_of, parts = 0, [], []
+    for n_groups, (_, _, hcols, donor, owner, rec) in enumerate(PT.group_columns(M, donor_samples, max_haps), 1):
         rec = rec[want[hcols[rec]]]
         if not len(rec):
             continue
-        donor = np.repeat(np.isin(cols, donor_samples), 2).astype(np.uint8)
-        owner = np.repeat(np.arange(len(cols), dtype=np.int32), 2)
         parts.append(dose(np.ascontiguousarray(hap[:, hcols]), donor, owner, rec.astype(np.int32), rho, theta))
         cols_of.append(hcols[rec])
     if not parts:
-        return np.zeros(0, dtype=np.int64), np.zeros((0, hap.shape[0]), dtype=np.float32), np.zeros(0), np.zeros(0, dtype=np.int32), len(groups)
+        return np.zeros(0, dtype=np.int64), np.zeros((0, hap.shape[0]), dtype=np.float32), np.zeros(0), np.zeros(0, dtype=np.int32), n_groups
     cols = np.concatenate(cols_of)
     order = np.argsort(cols, kind="stable")
     d, ll, nd = (np.concatenate([p[i] for p in parts])[order] for i in range(3))
-    return cols[order], d, ll, nd, len(groups)
+    return cols[order], d, ll, nd, n_groups
 
 
 def donor_frequency(hap, donor_cols):
@@ -258,27 +206,17 @@ def impute(hap, donors, candidates, samples, sites, out=None, counts=None, mode=
     donors, candidates = np.asarray(donors, dtype=np.int64), np.asarray(candidates, dtype=np.int64)
     if K == 0:
         raise SystemExit(f"{PROG}: no site is left: nothing to impute")
-    if not (np.isfinite(switch) and switch > 0):
-        raise SystemExit(f"{PROG}: --switch must be a positive number")
-    if em_rounds < 0 or em_sample < 1:
-        raise SystemExit(f"{PROG}: --em_rounds must be >= 0 and --em_sample >= 1")
-    if theta is None:
-        theta = PT.default_theta(2 * len(donors))
-    if not PT.THETA_MIN <= theta <= PT.THETA_MAX:
-        raise SystemExit(f"{PROG}: --theta must be {PT.THETA_MIN} .. {PT.THETA_MAX}")
-    if host:
-        copy = lambda *six: PT.copy_host(*six, dtype=dtype)
-        dose = lambda *six: dose_host(*six, dtype=dtype)
-    else:
+    theta = PT.checked_options(PROG, switch, em_rounds, em_sample, theta, 2 * len(donors))
+    if not host:
         B.require_gpu(PROG, LAUNCH)
-        copy = lambda *six: PT.copy_device(*six, budget=budget, device=device)
-        dose = lambda *six: dose_device(*six, budget=budget, device=device)
+    copy = PT.model_form(PT.copy_host, PT.copy_device, host, dtype, budget, device)
+    dose = PT.model_form(dose_host, dose_device, host, dtype, budget, device)
     try:
         g, first = PT.site_gaps(sites["chrom"], sites["pos"], K, uniform)
     except ValueError as e:
         raise SystemExit(f"{PROG}: {e}") from None
 
-    ccols = np.stack([2 * candidates, 2 * candidates + 1], axis=1).reshape(-1)
+    ccols = PT.hap_cols(candidates)
     truth = None
     if check_mask is not None:
         hidden = (np.random.default_rng(seed).random((K, len(ccols))) < check_mask) & (hap[:, ccols] >= 0)
@@ -307,7 +245,7 @@ def impute(hap, donors, candidates, samples, sites, out=None, counts=None, mode=
              f"launch group(s)", f"theta {theta!r}, switch rate {lam!r} after {em_rounds} rounds, ll {summary['ll']!r}",
              f"{summary['imputed_alleles']} of {summary['missing_alleles']} missing alleles have a dose"]
     if truth is not None:
-        freq = np.broadcast_to(donor_frequency(hap, np.stack([2 * donors, 2 * donors + 1], axis=1).reshape(-1))[:, None], truth.shape)
+        freq = np.broadcast_to(donor_frequency(hap, PT.hap_cols(donors))[:, None], truth.shape)
         at = hidden & np.isfinite(doses.T) & np.isfinite(freq)
         model, base = scores(doses.T[at], truth[at]), scores(freq[at], truth[at])
         summary.update(dict(zip(CHECKED, (int(hidden.sum()), int(at.sum()), *model, *base))))
@@ -323,7 +261,7 @@ def impute(hap, donors, candidates, samples, sites, out=None, counts=None, mode=
             G.write_callset_zarr(store, gt.reshape(K, len(candidates), 2), np.asarray(sites["pos"], dtype=np.int32), samples,
                                  chrom=sites["chrom"], ref=sites["ref"], alt=sites["alt"])
             G.write_dosage_zarr(store, ds)
-        write_atomic(out + "_impute_history.txt", "round\tswitch\tll\n" + "".join(f"{t}\t{l!r}\t{v!r}\n" for t, l, v in history))
+        PT.write_history(out + "_impute_history.txt", history)
         write_atomic(out + "_impute_summary.json", json.dumps(summary, indent=1) + "\n")
     if not silence:
         for line in lines:
@@ -342,23 +280,14 @@ def build_parser():
     p.add_argument("--panel", default=None, help="phased reference panel, a VCF or a zarr store (a directory): impute its sites "
                                                  "for the samples of --vcf / --zarr.  Without it the missing alleles are filled")
     p.add_argument("--out", required=True, help="output stem")
-    p.add_argument("--switch", default=0.01, type=float, help="first switch rate lambda a mean gap (default 0.01)")
-    p.add_argument("--em_rounds", default=3, type=int, help="rounds that re-estimate the switch rate (default 3)")
-    p.add_argument("--em_sample", default=256, type=int, help="individuals used as recipients of those rounds at most (default 256)")
-    p.add_argument("--theta", default=None, type=float, help=f"mismatch probability, {PT.THETA_MIN} .. {PT.THETA_MAX} (default: Li & "
-                                                             "Stephens' from the number of donor haplotypes)")
-    p.add_argument("--uniform", default=False, action="store_true", help="every site one mean gap from the one before it")
-    p.add_argument("--max_donors", default=None, type=int, metavar="M", help="take every ceil(n / M)-th candidate sample as a donor")
-    p.add_argument("--max_haps", default=MAX_HAPS, type=int, help=f"haplotype columns of a launch at most (default and limit {MAX_HAPS})")
+    PT.add_model_arguments(p)
     p.add_argument("--fill_calls", default=False, action="store_true",
                    help="calldata/GT: every missing allele that has a dose becomes dose >= 0.5 (default: the input calls)")
     p.add_argument("--check_mask", default=None, type=float, metavar="F",
                    help="check run: hide every observed allele with probability F, impute it and report the errors; writes the summary only")
     p.add_argument("--seed", default=None, type=int, help="seed of the --check_mask draw")
-    p.add_argument("--budget_gb", default=4.0, type=float, help="device scratch and dose rows of a launch at most, GiB (default 4)")
-    p.add_argument("--host", default=False, action="store_true", help="the NumPy form in float64 instead of the GPU")
-    p.add_argument("--host_dtype", default="float64", choices=("float64", "float32"),
-                   help="the arithmetic of --host (float32: what the device's round-off is measured against)")
+    PT.add_path_arguments(p, "device scratch and dose rows of a launch at most, GiB (default 4)",
+                          "the NumPy form in float64 instead of the GPU")
     p.add_argument("--gpu_number", default=None, type=str, help="the GPU to use (sets HIP_VISIBLE_DEVICES)")
     p.add_argument("--silence", default=False, action="store_true", help="no terminal output")
     return p
@@ -407,16 +336,13 @@ def main(argv=None):
         theirs, counts = match_panel(panel, target)
         counts["multiallelic_dropped"] = dropped + more
         donors = thin(len(panel["samples"]))
-        pcols = np.stack([2 * donors, 2 * donors + 1], axis=1).reshape(-1)
+        pcols = PT.hap_cols(donors)
         hap = np.concatenate([panel["gt"].reshape(len(panel["pos"]), -1)[:, pcols], theirs], axis=1)
         donors, candidates = np.arange(len(donors)), len(donors) + np.arange(Nt)
         room = 2 * len(donors) + 2
     if Nt < 1 or len(donors) < 1 or (a.panel is None and Nt < 2):
         raise SystemExit(f"{PROG}: {Nt} samples and {len(donors)} donor samples: nobody to copy from")
-    if room > a.max_haps:
-        raise SystemExit(f"{PROG}: {2 * len(donors)} donor haplotypes and a recipient do not fit {a.max_haps} columns (--max_haps, at "
-                         f"most {MAX_HAPS}: a wave holds a value a column in registers); pass --max_donors M to take every "
-                         f"ceil(n / M)-th sample as a donor, M <= {a.max_haps // 2 - 1}")
+    PT.check_room(PROG, room, len(donors), a.max_haps, "sample")
     try:
         impute(hap, donors, candidates, target["samples"], sites, a.out, counts, mode, a.switch, a.em_rounds, a.em_sample, a.theta,
                a.uniform, a.max_haps, a.fill_calls, a.check_mask, a.seed, a.host, a.silence, budget=int(a.budget_gb * (1 << 30)),

@@ -316,12 +316,12 @@ def load_genotypes():
         loaded, _PRELOADED = _PRELOADED, None
         if loaded is not None and loaded[0] == args.vcf:
             if _keep_model():
-                _VARIANTS = _site_columns(loaded[3])
+                _VARIANTS = G.site_columns(loaded[3])
             return loaded[1], loaded[2]
         print("reading VCF")
         vcf = G.read_vcf(args.vcf, sites=_keep_model())
         if _keep_model():
-            _VARIANTS = _site_columns(vcf)
+            _VARIANTS = G.site_columns(vcf)
         return vcf["calldata/GT"], vcf["samples"]
     if args.matrix is not None:
         if _keep_model():
@@ -333,26 +333,17 @@ def load_genotypes():
 _VARIANTS = None       # --keep_model: {chrom, pos, ref, alt} of every input variant (load_genotypes / _variant_table)
 
 
-def _site_columns(d):
-    """read_vcf(sites=True) / zarr_sites dict -> {chrom, pos, ref, alt}: ALT[0] of each variant."""
-    alt = np.asarray(d["variants/ALT"], dtype=object)
-    return {"chrom": np.asarray(d["variants/CHROM"], dtype=object).astype(str),
-            "pos": np.asarray(d["variants/POS"], dtype=np.int64),
-            "ref": np.asarray(d["variants/REF"], dtype=object).astype(str),
-            "alt": (alt[:, 0] if alt.ndim == 2 else alt).astype(str)}
-
-
 def _variant_table():
     """--keep_model: the identity of every variant of the run's genotype source.  A --matrix column is its header name
     (POS -1, no alleles); a zarr store must hold variants/CHROM, REF and ALT."""
     if args.zarr is not None:
         try:
-            return _site_columns(G.zarr_sites(G.open_group(args.zarr, mode="r")))
+            return G.site_columns(G.zarr_sites(G.open_group(args.zarr, mode="r")))
         except KeyError as e:
             raise SystemExit(f"--keep_model: {args.zarr} has no {e.args[0]}: the model file records CHROM, POS, REF and ALT "
                              "of every site") from None
     if args.vcf is not None:
-        return _site_columns(G.read_vcf(args.vcf, sites=True))
+        return G.site_columns(G.read_vcf(args.vcf, sites=True))
     names = G.matrix_sites(args.matrix).astype(str)
     empty = np.full(len(names), "", dtype=str)
     return {"chrom": names, "pos": np.full(len(names), -1, np.int64), "ref": empty, "alt": empty}

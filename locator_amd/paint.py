@@ -145,62 +145,90 @@ def _copy_batch(h, dn, rcols, rho, theta, dtype):
     return sa / f(K), ca, ll
 
 
-def copy_host(h, donor, owner, rec, rho, theta, dtype=np.float64):
-    """(share [R][H] dtype, chunks [R][H] dtype, ll [R] float64, n_donors [R] int32): the definition in the module text."""
+def hap_cols(samples):
+    """The haplotype columns 2 s, 2 s + 1 of the samples s, in their order."""
+    samples = np.asarray(samples)
+    return np.stack([2 * samples, 2 * samples + 1], axis=1).reshape(-1)
+
+
+def _outputs(specs, R, H, K):
+    """The outputs of a model function before a recipient ran.  specs: (columns "H" or "K", dtype, the value an unrun row holds)
+    an output."""
+    return [np.full((R, {"H": H, "K": K}[cols]), value, dtype=dtype) for cols, dtype, value in specs]
+
+
+def _host_model(batch, specs, h, donor, owner, rec, rho, theta, dtype):
+    """copy_host and impute.dose_host: (the outputs of `specs`, ll [R] float64, n_donors [R] int32) from `batch` (_copy_batch,
+    impute._dose_batch) over the recipients that have a donor, HOST_BATCH_BYTES of a-hat at a time."""
     h, donor, owner, rec, rho = _check(h, donor, owner, rec, rho, theta)
     K, H, R = h.shape[0], len(donor), len(rec)
-    share, chunks = np.zeros((R, H), dtype=dtype), np.zeros((R, H), dtype=dtype)
+    outs = _outputs(specs, R, H, K)
     ll, n_donors = np.zeros(R), np.zeros(R, dtype=np.int32)
     if K == 0 or R == 0:
-        return share, chunks, ll, n_donors
+        return (*outs, ll, n_donors)
     dn = donor[None, :] & (owner[None, :] != owner[rec][:, None])
     n_donors[:] = dn.sum(axis=1)
     live = np.flatnonzero(n_donors > 0)
     step = max(1, HOST_BATCH_BYTES // (K * H * np.dtype(dtype).itemsize))
     for a in range(0, len(live), step):
         rows = live[a:a + step]
-        share[rows], chunks[rows], ll[rows] = _copy_batch(h, dn[rows], rec[rows], rho, theta, dtype)
-    return share, chunks, ll, n_donors
+        *got, ll[rows] = batch(h, dn[rows], rec[rows], rho, theta, dtype)
+        for out, part in zip(outs, got):
+            out[rows] = part
+    return (*outs, ll, n_donors)
+
+
+def copy_host(h, donor, owner, rec, rho, theta, dtype=np.float64):
+    """(share [R][H] dtype, chunks [R][H] dtype, ll [R] float64, n_donors [R] int32): the definition in the module text."""
+    return _host_model(_copy_batch, (("H", dtype, 0), ("H", dtype, 0)), h, donor, owner, rec, rho, theta, dtype)
 
 
 # ---------------------------------------------------------------- the device form
 
-def copy_device(h, donor, owner, rec, rho, theta, block=0, pitch=None, pad_fill=-1, fill=None, budget=4 << 30, device="cuda:0"):
-    """copy_host's answer from loc_paint_copy launches (share and chunks float32), the recipients in batches whose scratch
-    stays within `budget` bytes.  fill: a 32-bit pattern that scratch and the outputs hold before a launch (tests)."""
-    import torch
+def _device_model(entry, specs, site_bytes, h, donor, owner, rec, rho, theta, block, pitch, pad_fill, fill, budget, device):
+    """copy_device and impute.dose_device: _host_model's answer from launches of the entry point `entry`, which takes the
+    outputs of `specs` before ll.  The recipients go in batches whose scratch, and site_bytes a site of a recipient beside it,
+    stay within `budget` bytes; an output without columns (K = 0) is not copied back."""
+    import torch as t
     from . import _device as D, _lib
     lib = _lib.load()
     h, dflag, owner, rec, rho = _check(h, donor, owner, rec, rho, theta)
     K, H, R = h.shape[0], len(dflag), len(rec)
     buf = B.padded(np.ascontiguousarray(h[:, :H]), pitch, pad_fill)
-    t = torch
     with t.cuda.device(device):
         d_h, d_donor, d_owner = D.put(buf, np.int8, device), D.put(dflag, np.uint8, device), D.put(owner, np.int32, device)
         d_rho = D.put(rho if K else np.zeros(1), np.float32, device)
         one = int(lib.loc_paint_work_bytes(H, K, 1, int(block)))
         if one < 0:
             _lib.check(-1, "loc_paint_work_bytes")
-        step = max(1, int(budget) // max(one, 1))
-        share, chunks = np.zeros((R, H), dtype=np.float32), np.zeros((R, H), dtype=np.float32)
+        step = max(1, int(budget) // max(one + site_bytes * K, 1))
+        outs = _outputs(specs, R, H, K)
         ll, n_donors = np.zeros(R), np.zeros(R, dtype=np.int32)
         for a in range(0, R, step):
             n = min(step, R - a)
             d_rec = D.put(rec[a:a + n], np.int32, device)
-            d_share = t.empty((n, H), dtype=t.float32, device=device)
-            d_chunks = t.empty((n, H), dtype=t.float32, device=device)
+            d_outs = [t.empty((n, max(out.shape[1], 1)), dtype=getattr(t, out.dtype.name), device=device) for out in outs]
             d_ll = t.empty(n, dtype=t.float64, device=device)
             d_nd = t.empty(n, dtype=t.int32, device=device)
             d_work, work_bytes = D.work_buffer(lib, "loc_paint_work_bytes", H, K, n, int(block), device=device, fill=fill)
-            D.prefill((d_share, d_chunks, d_ll, d_nd), fill)
-            _lib.check(lib.loc_paint_copy(d_h.data_ptr(), H, K, int(buf.shape[1]), d_donor.data_ptr(), d_owner.data_ptr(),
-                                          d_rec.data_ptr(), n, d_rho.data_ptr(), float(theta), int(block), d_share.data_ptr(),
-                                          d_chunks.data_ptr(), d_ll.data_ptr(), d_nd.data_ptr(), d_work.data_ptr(), work_bytes,
-                                          D.stream()), "loc_paint_copy")
-            share[a:a + n], chunks[a:a + n] = d_share.cpu().numpy(), d_chunks.cpu().numpy()
+            D.prefill((*d_outs, d_ll, d_nd), fill)
+            _lib.check(getattr(lib, entry)(d_h.data_ptr(), H, K, int(buf.shape[1]), d_donor.data_ptr(), d_owner.data_ptr(),
+                                           d_rec.data_ptr(), n, d_rho.data_ptr(), float(theta), int(block),
+                                           *(d.data_ptr() for d in d_outs), d_ll.data_ptr(), d_nd.data_ptr(), d_work.data_ptr(),
+                                           work_bytes, D.stream()), entry)
+            for out, d in zip(outs, d_outs):
+                if out.shape[1]:
+                    out[a:a + n] = d.cpu().numpy()
             ll[a:a + n], n_donors[a:a + n] = d_ll.cpu().numpy(), d_nd.cpu().numpy()
             del d_work
-    return share, chunks, ll, n_donors
+    return (*outs, ll, n_donors)
+
+
+def copy_device(h, donor, owner, rec, rho, theta, block=0, pitch=None, pad_fill=-1, fill=None, budget=4 << 30, device="cuda:0"):
+    """copy_host's answer from loc_paint_copy launches (share and chunks float32), the recipients in batches whose scratch
+    stays within `budget` bytes.  fill: a 32-bit pattern that scratch and the outputs hold before a launch (tests)."""
+    return _device_model("loc_paint_copy", (("H", np.float32, 0), ("H", np.float32, 0)), 0, h, donor, owner, rec, rho, theta, block,
+                         pitch, pad_fill, fill, budget, device)
 
 
 # ---------------------------------------------------------------- the driver's pieces
@@ -264,6 +292,15 @@ def launch_groups(N, donor_samples, max_haps):
     return groups
 
 
+def group_columns(N, donor_samples, max_haps):
+    """launch_groups as a launch takes them, a group a tuple: cols (its samples), at (where its recipient samples are in cols),
+    hcols (its haplotype columns of the whole matrix), donor and owner of its columns, rec (the recipients' columns in it)."""
+    for cols, recs in launch_groups(N, donor_samples, max_haps):
+        at = np.flatnonzero(np.isin(cols, recs))
+        yield (cols, at, hap_cols(cols), np.repeat(np.isin(cols, donor_samples), 2).astype(np.uint8),
+               np.repeat(np.arange(len(cols), dtype=np.int32), 2), hap_cols(at))
+
+
 def sample_weights(copy, hap, donor_samples, rho, theta, max_haps=MAX_HAPS, recipients=None):
     """The model over launch groups, folded to samples: (W [N][N] = the four haplotype shares of sample s in sample t summed,
     C [N][N] likewise of chunks, ll [2N], n_donors [2N], number of groups).  hap int8 [K][2N]; copy: copy_host or copy_device
@@ -273,23 +310,18 @@ def sample_weights(copy, hap, donor_samples, rho, theta, max_haps=MAX_HAPS, reci
     W, C = np.zeros((N, N)), np.zeros((N, N))
     ll, nd = np.zeros(2 * N), np.zeros(2 * N, dtype=np.int32)
     wanted = np.ones(N, dtype=bool) if recipients is None else np.isin(np.arange(N), recipients)
-    groups = launch_groups(N, donor_samples, max_haps)
-    for cols, recs in groups:
-        recs = recs[wanted[recs]]
-        if not len(recs):
+    n_groups = 0
+    for n_groups, (cols, at, hcols, donor, owner, rec) in enumerate(group_columns(N, donor_samples, max_haps), 1):
+        run = wanted[cols[at]]
+        at, rec = at[run], rec[np.repeat(run, 2)]
+        if not len(at):
             continue
-        hcols = np.stack([2 * cols, 2 * cols + 1], axis=1).reshape(-1)
-        donor = np.repeat(np.isin(cols, donor_samples), 2).astype(np.uint8)
-        owner = np.repeat(np.arange(len(cols), dtype=np.int32), 2)
-        at = np.flatnonzero(np.isin(cols, recs))
-        rec = np.stack([2 * at, 2 * at + 1], axis=1).reshape(-1)
         share, chunks, l, n = copy(np.ascontiguousarray(hap[:, hcols]), donor, owner, rec, rho, theta)
         fold = lambda m: np.asarray(m, dtype=np.float64).reshape(len(at), 2, len(cols), 2).sum(axis=(1, 3))
         W[np.ix_(cols[at], cols)] = fold(share)
         C[np.ix_(cols[at], cols)] = fold(chunks)
-        rows = np.stack([2 * cols[at], 2 * cols[at] + 1], axis=1).reshape(-1)
-        ll[rows], nd[rows] = l, n
-    return W, C, ll, nd, len(groups)
+        ll[hap_cols(cols[at])], nd[hap_cols(cols[at])] = l, n
+    return W, C, ll, nd, n_groups
 
 
 def estimate_switch(copy, hap, donors, g, first, switch, em_rounds, em_sample, theta, max_haps=MAX_HAPS, pool=None):
@@ -308,6 +340,39 @@ def estimate_switch(copy, hap, donors, g, first, switch, em_rounds, em_sample, t
     if history:
         lam = max(history, key=lambda r: (r[2], -r[0]))[1]
     return lam, history, em_recipients
+
+
+def checked_options(prog, switch, em_rounds, em_sample, theta, n_donor_haps):
+    """The refusals of the model's options that the paint and impute commands share; returns theta, the default for
+    n_donor_haps donor haplotypes where none is given."""
+    if not (np.isfinite(switch) and switch > 0):
+        raise SystemExit(f"{prog}: --switch must be a positive number")
+    if em_rounds < 0 or em_sample < 1:
+        raise SystemExit(f"{prog}: --em_rounds must be >= 0 and --em_sample >= 1")
+    if theta is None:
+        theta = default_theta(n_donor_haps)
+    if not THETA_MIN <= theta <= THETA_MAX:
+        raise SystemExit(f"{prog}: --theta must be {THETA_MIN} .. {THETA_MAX}")
+    return theta
+
+
+def check_room(prog, room, n_donors, max_haps, of):
+    """The refusal of donors that leave no column of a launch to a recipient.  of: whom --max_donors thins, in the command's words."""
+    if room > max_haps:
+        raise SystemExit(f"{prog}: {2 * n_donors} donor haplotypes and a recipient do not fit {max_haps} columns (--max_haps, at "
+                         f"most {MAX_HAPS}: a wave holds a value a column in registers); pass --max_donors M to take every "
+                         f"ceil(n / M)-th {of} as a donor, M <= {max_haps // 2 - 1}")
+
+
+def model_form(on_host, on_device, host, dtype, budget, device):
+    """on_host in `dtype` or on_device within `budget` on `device`, as a function of the model's six leading arguments."""
+    if host:
+        return lambda *six: on_host(*six, dtype=dtype)
+    return lambda *six: on_device(*six, budget=budget, device=device)
+
+
+def write_history(path, history):
+    write_atomic(path, "round\tswitch\tll\n" + "".join(f"{t}\t{l!r}\t{v!r}\n" for t, l, v in history))
 
 
 # the placement from a sample-by-sample weight is shared with the ibd command: baselines.py holds it, these are its names here
@@ -330,10 +395,6 @@ def paint(hap, c, P, samples, locs, chrom=None, pos=None, out=None, switch=0.01,
         raise SystemExit(f"{PROG}: {H} haplotype columns for {len(samples)} samples: needs two a sample and two samples at least")
     if K == 0:
         raise SystemExit(f"{PROG}: no site is left after the filters: nothing to paint")
-    if not (np.isfinite(switch) and switch > 0):
-        raise SystemExit(f"{PROG}: --switch must be a positive number")
-    if em_rounds < 0 or em_sample < 1:
-        raise SystemExit(f"{PROG}: --em_rounds must be >= 0 and --em_sample >= 1")
     if not 2 <= max_haps <= MAX_HAPS:
         raise SystemExit(f"{PROG}: --max_haps must be 2 .. {MAX_HAPS}")
     if max_donors is not None and max_donors < 1:
@@ -343,21 +404,13 @@ def paint(hap, c, P, samples, locs, chrom=None, pos=None, out=None, switch=0.01,
         locs, located = B.located_mask(locs, N, PROG)
     pool = np.arange(N) if located is None else np.flatnonzero(located)
     donors = pool if max_donors is None else pool[::-(-len(pool) // max_donors)]
-    if 2 * len(donors) + (2 if len(donors) < N else 0) > max_haps:
-        raise SystemExit(f"{PROG}: {2 * len(donors)} donor haplotypes and a recipient do not fit {max_haps} columns (--max_haps, at "
-                         f"most {MAX_HAPS}: a wave holds a value a column in registers); pass --max_donors M to take every "
-                         f"ceil(n / M)-th of the {len(pool)} candidate samples as a donor, M <= {max_haps // 2 - 1}")
-    if theta is None:
-        theta = default_theta(2 * len(donors))
-    if not THETA_MIN <= theta <= THETA_MAX:
-        raise SystemExit(f"{PROG}: --theta must be {THETA_MIN} .. {THETA_MAX}")
+    check_room(PROG, 2 * len(donors) + (2 if len(donors) < N else 0), len(donors), max_haps, f"of the {len(pool)} candidate samples")
+    theta = checked_options(PROG, switch, em_rounds, em_sample, theta, 2 * len(donors))
     if k != "auto" and not 1 <= int(k) <= kmax or not 1 <= kmax <= B.KMAX_LIMIT:
         raise SystemExit(f"{PROG}: --kmax must be 1 .. {B.KMAX_LIMIT} and --k `auto` or 1 .. --kmax")
-    if host:
-        copy = lambda *six: copy_host(*six, dtype=dtype)
-    else:
+    if not host:
         B.require_gpu(PROG, LAUNCH)
-        copy = lambda *six: copy_device(*six, budget=budget, device=device)
+    copy = model_form(copy_host, copy_device, host, dtype, budget, device)
     g, first = site_gaps(chrom, pos, K, uniform)
 
     lam, history, em_recipients = estimate_switch(copy, hap, donors, g, first, switch, em_rounds, em_sample, theta, max_haps)
@@ -374,7 +427,7 @@ def paint(hap, c, P, samples, locs, chrom=None, pos=None, out=None, switch=0.01,
              f"theta {theta!r}, switch rate {lam!r} after {em_rounds} rounds, ll {own['ll']!r}, {own['mean_chunks']!r} chunks a "
              f"haplotype", *lines]
     if out is not None:
-        write_atomic(out + "_paint_history.txt", "round\tswitch\tll\n" + "".join(f"{t}\t{l!r}\t{v!r}\n" for t, l, v in history))
+        write_history(out + "_paint_history.txt", history)
         rows = ["sampleID\trank\tdonorID\tshare\n"]
         for s in range(N):
             for r in range(nbr.shape[1]):
@@ -396,7 +449,8 @@ def paint(hap, c, P, samples, locs, chrom=None, pos=None, out=None, switch=0.01,
 
 # ---------------------------------------------------------------- command
 
-def _own_arguments(p):
+def add_model_arguments(p):
+    """The model's options of the paint and impute commands."""
     p.add_argument("--switch", default=0.01, type=float, help="first switch rate lambda a mean gap (default 0.01)")
     p.add_argument("--em_rounds", default=3, type=int, help="rounds that re-estimate the switch rate (default 3)")
     p.add_argument("--em_sample", default=256, type=int, help="individuals used as recipients of those rounds at most (default 256)")
@@ -405,16 +459,25 @@ def _own_arguments(p):
     p.add_argument("--uniform", default=False, action="store_true", help="every site one mean gap from the one before it")
     p.add_argument("--max_donors", default=None, type=int, metavar="M", help="take every ceil(n / M)-th candidate sample as a donor")
     p.add_argument("--max_haps", default=MAX_HAPS, type=int, help=f"haplotype columns of a launch at most (default and limit {MAX_HAPS})")
+
+
+def add_path_arguments(p, budget_help, host_help):
+    """--budget_gb, --host and --host_dtype of the two commands; what a launch's budget holds and what --host changes differ."""
+    p.add_argument("--budget_gb", default=4.0, type=float, help=budget_help)
+    p.add_argument("--host", default=False, action="store_true", help=host_help)
+    p.add_argument("--host_dtype", default="float64", choices=("float64", "float32"),
+                   help="the arithmetic of --host (float32: what the device's round-off is measured against)")
+
+
+def _own_arguments(p):
+    add_model_arguments(p)
     B.add_k_arguments(p, 16, "donor samples", "donors")
     p.add_argument("--longlat", default=False, action="store_true",
                    help="x / y are longitude / latitude degrees: errors are great-circle km (the mean stays planar)")
     p.add_argument("--keep_matrix", default=False, action="store_true",
                    help="keep the sample-level chunk lengths, chunk counts and the sample IDs in {out}_paint.npz")
-    p.add_argument("--budget_gb", default=4.0, type=float, help="device scratch of a launch at most, GiB (default 4)")
-    p.add_argument("--host", default=False, action="store_true",
-                   help="the NumPy form in float64 instead of the GPU (the files differ as the module text says)")
-    p.add_argument("--host_dtype", default="float64", choices=("float64", "float32"),
-                   help="the arithmetic of --host (float32: what the device's round-off is measured against)")
+    add_path_arguments(p, "device scratch of a launch at most, GiB (default 4)",
+                       "the NumPy form in float64 instead of the GPU (the files differ as the module text says)")
 
 
 def build_parser():

@@ -8,7 +8,8 @@ from locator_amd import _abi, _lib
 INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 HEADERS = {"ext": "locator_hip_query.h", "region": "locator_hip_regions.h", "neighbor": "locator_hip_neighbors.h",
            "pca": "locator_hip_pca.h", "ld": "locator_hip_ld.h", "spa": "locator_hip_spa.h", "admix": "locator_hip_admix.h",
-           "localpca": "locator_hip_localpca.h", "paint": "locator_hip_paint.h", "ibd": "locator_hip_ibd.h"}
+           "localpca": "locator_hip_localpca.h", "paint": "locator_hip_paint.h", "ibd": "locator_hip_ibd.h",
+           "impute": "locator_hip_impute.h"}
 
 
 def check_extension(tag, prototypes, constants):

@@ -108,9 +108,11 @@ def test_the_same_bits_whatever_scratch_held_and_whatever_is_appended():
     assert same_bits(device(case, budget=1), first)
 
 
-def _raw(lib, t, H, K, R, pitch, theta, block, rec=None, work_bytes=None, pattern=0x5a5a5a5a, null_dose=False, case=None):
+def _raw(lib, t, H, K, R, pitch, theta, block, rec=None, work_bytes=None, pattern=0x5a5a5a5a, null_dose=False, case=None, dose_off=0,
+         ll_off=0):
     """One direct call on buffers filled with a pattern, dose 64 floats inside a larger buffer: (return code, [the whole dose
-    buffer, ll, n_donors] as int32 views).  case: its haplotypes, flags and rho instead of zeros, ones and 0.1."""
+    buffer, ll, n_donors] as int32 views).  case: its haplotypes, flags and rho instead of zeros, ones and 0.1.  dose_off, ll_off:
+    bytes by which dose and ll are passed further into their buffers (ll's holds a word more than it needs)."""
     dev = "cuda:0"
     put = lambda v, dt: t.from_numpy(np.ascontiguousarray(v, dtype=dt)).to(dev)
     if case is None:
@@ -122,14 +124,15 @@ def _raw(lib, t, H, K, R, pitch, theta, block, rec=None, work_bytes=None, patter
         h, donor, owner = put(IM.B.padded(case["h"], pitch), np.int8), put(case["donor"], np.uint8), put(case["owner"], np.int32)
         rho = put(case["rho"], np.float32)
     d_rec = t.tensor(list(range(R)) if rec is None else list(rec), dtype=t.int32, device=dev) if R else t.zeros(1, dtype=t.int32, device=dev)
-    outs = [t.empty(128 + max(R, 0) * max(K, 0), dtype=t.int32, device=dev), t.empty(2 * max(R, 1), dtype=t.int32, device=dev),
+    outs = [t.empty(128 + max(R, 0) * max(K, 0), dtype=t.int32, device=dev), t.empty(2 * max(R, 1) + 1, dtype=t.int32, device=dev),
             t.empty(max(R, 1), dtype=t.int32, device=dev)]
     for o in outs:
         o.fill_(int(np.array(pattern, dtype=np.uint32).view(np.int32)))
     need = int(lib.loc_paint_work_bytes(min(max(H, 1), PT.MAX_HAPS), max(K, 0), max(R, 0), max(block, 0)))
     work = t.empty(max(need // 4, 4), dtype=t.float32, device=dev)
     rc = lib.loc_impute_dose(h.data_ptr(), H, K, pitch, donor.data_ptr(), owner.data_ptr(), d_rec.data_ptr(), R, rho.data_ptr(),
-                             C.c_float(theta), block, None if null_dose else outs[0].data_ptr() + 4 * 64, outs[1].data_ptr(),
+                             C.c_float(theta), block, None if null_dose else outs[0].data_ptr() + 4 * 64 + dose_off,
+                             outs[1].data_ptr() + ll_off,
                              outs[2].data_ptr(), work.data_ptr(), need if work_bytes is None else work_bytes,
                              t.cuda.current_stream().cuda_stream)
     t.cuda.synchronize()
@@ -153,18 +156,21 @@ def test_every_dose_is_stored_and_nothing_around_them(K):
         assert same_bits([inner.view(np.float32).reshape(R, K)], device(case)[:1])
 
 
+OK = dict(H=8, K=5, R=3, pitch=16, theta=0.01, block=0)
+BAD = [dict(H=PT.MAX_HAPS + 1, pitch=PT.MAX_HAPS + 16), dict(H=0), dict(rec=[0, 8, 1]), dict(rec=[-1, 0, 1]), dict(theta=0.6),
+       dict(theta=5e-8), dict(theta=float("nan")), dict(pitch=0), dict(pitch=24), dict(H=20, pitch=16), dict(work_bytes=16),
+       dict(block=-1), dict(K=-1), dict(R=-1), dict(null_dose=True)]
+
+
 def test_bad_arguments_launch_nothing_and_empty_inputs_are_as_specified():
     import torch as t
     from locator_amd import _lib
     lib = _lib.load()
     pat = np.array(0x5a5a5a5a, dtype=np.uint32).view(np.int32)
-    ok = dict(H=8, K=5, R=3, pitch=16, theta=0.01, block=0)
+    ok = OK
     rc, outs = _raw(lib, t, **ok)
     assert rc == 0 and not any((o == pat).all() for o in outs)
-    bad = [dict(H=PT.MAX_HAPS + 1, pitch=PT.MAX_HAPS + 16), dict(H=0), dict(rec=[0, 8, 1]), dict(rec=[-1, 0, 1]), dict(theta=0.6),
-           dict(theta=5e-8), dict(theta=float("nan")), dict(pitch=0), dict(pitch=24), dict(H=20, pitch=16), dict(work_bytes=16),
-           dict(block=-1), dict(K=-1), dict(R=-1), dict(null_dose=True)]
-    for change in bad:
+    for change in BAD:
         rc, outs = _raw(lib, t, **{**ok, **change})
         assert rc == -1 and lib.loc_last_error(), change
         assert all((o == pat).all() for o in outs), change
@@ -174,6 +180,25 @@ def test_bad_arguments_launch_nothing_and_empty_inputs_are_as_specified():
     assert rc == 0 and (outs[0] == pat).all() and not outs[1][:6].any() and not outs[2][:3].any()      # ll, n_donors zeros, no dose
     dose, ll, nd = IM.dose_device(np.zeros((0, 8), dtype=np.int8), *U.everyone(4), np.zeros(0), 0.01)
     assert dose.shape == (8, 0) and not ll.any() and not nd.any()
+
+
+def test_a_refusal_speaks_for_its_own_entry_point_and_misaligned_buffers_are_refused():
+    """The launcher's refusals are shared with loc_paint_copy: every message begins with this entry point's name, and the null and
+    alignment messages are the literal texts of the launcher before the refusals were shared."""
+    import torch as t
+    from locator_amd import _lib
+    lib = _lib.load()
+    pat = np.array(0x5a5a5a5a, dtype=np.uint32).view(np.int32)
+    said = lambda: lib.loc_last_error().decode()
+    for change in BAD:
+        rc, outs = _raw(lib, t, **{**OK, **change})
+        assert rc == -1 and said().startswith("loc_impute_dose: "), (change, said())
+        if "null_dose" in change:
+            assert said() == "loc_impute_dose: null buffer"
+    for change in (dict(ll_off=4), dict(dose_off=2)):                             # ll at 4 mod 8, dose at 2 mod 4
+        rc, outs = _raw(lib, t, **{**OK, **change})
+        assert rc == -1 and all((o == pat).all() for o in outs), change
+        assert said() == "loc_impute_dose: dose, n_donors, rho, owner and rec must be multiples of 4 bytes, ll of 8", (change, said())
 
 
 def test_the_register_limit():

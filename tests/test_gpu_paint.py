@@ -109,25 +109,32 @@ def test_a_long_stretch_without_a_switch_underflows_to_zeros_not_to_nan():
     assert same_bits(device(case, block=1), got) and same_bits(device(case, block=200), got)
 
 
-def _raw(lib, t, H, K, R, pitch, theta, block, rec=None, work_bytes=None, pattern=0x5a5a5a5a):
-    """One direct call on buffers filled with a pattern: (return code, share, chunks, ll, n_donors as int32 views)."""
+def _raw(lib, t, H, K, R, pitch, theta, block, rec=None, work_bytes=None, pattern=0x5a5a5a5a, null_share=False, share_off=0, ll_off=0):
+    """One direct call on buffers filled with a pattern: (return code, share, chunks, ll, n_donors as int32 views).  share_off,
+    ll_off: bytes by which share and ll are passed off the start of their buffers, which hold a word more than they need."""
     dev = "cuda:0"
     h = t.zeros((max(K, 1), max(pitch, 16)), dtype=t.int8, device=dev)
     donor = t.ones(max(H, 1), dtype=t.uint8, device=dev)
     owner = (t.arange(max(H, 1), dtype=t.int32, device=dev) // 2).contiguous()
     d_rec = t.tensor(list(range(R)) if rec is None else rec, dtype=t.int32, device=dev) if R else t.zeros(1, dtype=t.int32, device=dev)
     rho = t.full((max(K, 1),), 0.1, dtype=t.float32, device=dev)
-    outs = [t.empty(max(R * max(H, 1), 1), dtype=t.int32, device=dev) for _ in range(2)]
-    outs += [t.empty(2 * max(R, 1), dtype=t.int32, device=dev), t.empty(max(R, 1), dtype=t.int32, device=dev)]
+    outs = [t.empty(max(R * max(H, 1), 1) + 1, dtype=t.int32, device=dev) for _ in range(2)]
+    outs += [t.empty(2 * max(R, 1) + 1, dtype=t.int32, device=dev), t.empty(max(R, 1), dtype=t.int32, device=dev)]
     for o in outs:
         o.fill_(int(np.array(pattern, dtype=np.uint32).view(np.int32)))
     need = int(lib.loc_paint_work_bytes(min(max(H, 1), PT.MAX_HAPS), max(K, 0), max(R, 0), max(block, 0)))
     work = t.empty(max(need // 4, 4), dtype=t.float32, device=dev)
     rc = lib.loc_paint_copy(h.data_ptr(), H, K, pitch, donor.data_ptr(), owner.data_ptr(), d_rec.data_ptr(), R, rho.data_ptr(),
-                            C.c_float(theta), block, outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), outs[3].data_ptr(),
-                            work.data_ptr(), need if work_bytes is None else work_bytes, t.cuda.current_stream().cuda_stream)
+                            C.c_float(theta), block, None if null_share else outs[0].data_ptr() + share_off, outs[1].data_ptr(),
+                            outs[2].data_ptr() + ll_off, outs[3].data_ptr(), work.data_ptr(), need if work_bytes is None else work_bytes, t.cuda.current_stream().cuda_stream)
     t.cuda.synchronize()
     return rc, [o.cpu().numpy() for o in outs]
+
+
+OK = dict(H=8, K=5, R=3, pitch=16, theta=0.01, block=0)
+BAD = [dict(H=PT.MAX_HAPS + 1, pitch=PT.MAX_HAPS + 16), dict(H=0), dict(rec=[0, 8, 1]), dict(rec=[-1, 0, 1]), dict(theta=0.6),
+       dict(theta=5e-8), dict(theta=float("nan")), dict(pitch=0), dict(pitch=24), dict(H=20, pitch=16), dict(work_bytes=16),
+       dict(block=-1), dict(K=-1), dict(R=-1), dict(null_share=True)]
 
 
 def test_bad_arguments_launch_nothing_and_empty_inputs_are_as_specified():
@@ -135,13 +142,10 @@ def test_bad_arguments_launch_nothing_and_empty_inputs_are_as_specified():
     from locator_amd import _lib
     lib = _lib.load()
     pat = np.array(0x5a5a5a5a, dtype=np.uint32).view(np.int32)
-    ok = dict(H=8, K=5, R=3, pitch=16, theta=0.01, block=0)
+    ok = OK
     rc, outs = _raw(lib, t, **ok)
     assert rc == 0 and not any((o == pat).all() for o in outs)
-    bad = [dict(H=PT.MAX_HAPS + 1, pitch=PT.MAX_HAPS + 16), dict(H=0), dict(rec=[0, 8, 1]), dict(rec=[-1, 0, 1]), dict(theta=0.6),
-           dict(theta=5e-8), dict(theta=float("nan")), dict(pitch=0), dict(pitch=24), dict(H=20, pitch=16), dict(work_bytes=16),
-           dict(block=-1), dict(K=-1), dict(R=-1)]
-    for change in bad:
+    for change in BAD:
         rc, outs = _raw(lib, t, **{**ok, **change})
         assert rc == -1 and lib.loc_last_error(), change
         assert all((o == pat).all() for o in outs), change
@@ -152,6 +156,25 @@ def test_bad_arguments_launch_nothing_and_empty_inputs_are_as_specified():
     assert rc == 0 and not outs[0][:24].any() and not outs[1][:24].any() and not outs[2][:6].any()
     share, chunks, ll, nd = PT.copy_host(np.zeros((0, 8), dtype=np.int8), *U.everyone(4), np.zeros(0), 0.01)
     assert share.shape == (8, 8) and not share.any() and not chunks.any() and not ll.any()
+
+
+def test_a_refusal_speaks_for_its_own_entry_point_and_misaligned_buffers_are_refused():
+    """The launcher's refusals are shared with loc_impute_dose: every message begins with this entry point's name, and the null and
+    alignment messages are the literal texts of the launcher before the refusals were shared."""
+    import torch as t
+    from locator_amd import _lib
+    lib = _lib.load()
+    pat = np.array(0x5a5a5a5a, dtype=np.uint32).view(np.int32)
+    said = lambda: lib.loc_last_error().decode()
+    for change in BAD:
+        rc, outs = _raw(lib, t, **{**OK, **change})
+        assert rc == -1 and said().startswith("loc_paint_copy: "), (change, said())
+        if "null_share" in change:
+            assert said() == "loc_paint_copy: null buffer"
+    for change in (dict(ll_off=4), dict(share_off=2)):                            # ll at 4 mod 8, share at 2 mod 4
+        rc, outs = _raw(lib, t, **{**OK, **change})
+        assert rc == -1 and all((o == pat).all() for o in outs), change
+        assert said() == "loc_paint_copy: share, chunks, n_donors, rho, owner and rec must be multiples of 4 bytes, ll of 8", (change, said())
 
 
 def test_the_register_limit():

@@ -1,11 +1,10 @@
-"""The impute command without a GPU: the binding through _abi's second table, the NumPy definition (the exact posterior by
+"""The impute command without a GPU: the binding through _abi's table, the NumPy definition (the exact posterior by
 enumeration, the closed form without linkage, the split at a certain switch, the structural NaNs, ll and n_donors of copy_host),
 the quality of the dose against the donors' allele frequency, the --host command in fill and panel mode, the refusals."""
 import ctypes as C
 import itertools
 import json
 import os
-import re
 import shutil
 import subprocess
 import sys
@@ -24,22 +23,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ------------------------------------------------------------------ the binding
-def test_the_second_table_binds_the_impute_header():
-    from locator_amd import _abi, _lib
-    from tests.abi_util import HEADERS
+def test_the_table_binds_the_impute_header():
+    from tests.abi_util import check_extension
     vp, i64, i, f = C.c_void_p, C.c_int64, C.c_int, C.c_float
     want = {"loc_impute_dose": (i, [vp, i, i64, i64, vp, vp, vp, i, vp, f, i, vp, vp, vp, vp, i64, vp])}
-    assert list(_abi.EXTENSIONS) == list(HEADERS) and list(_abi.LATER) == ["impute"]
-    ext = _abi.LATER["impute"]
-    assert ext.header == os.path.join(ROOT, "include", "locator_hip_impute.h")
-    src = re.sub(r"/\*.*?\*/", "", open(ext.header).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(loc_[a-z0-9_]+)\s*\(", src))) == sorted(want)
-    assert ext.prototypes == want and ext.constants == {"LOC_IMPUTE_STORE_RUN": 64} and _abi.LOC_IMPUTE_STORE_RUN == 64
-    others = [(_abi.CONSTANTS, _abi.PROTOTYPES)] + [(o.constants, o.prototypes) for o in _abi.EXTENSIONS.values()]
-    assert not any(set(want) & set(p) or set(ext.constants) & set(c) for c, p in others)
-    fn = _lib.load().loc_impute_dose                                              # the library exports it and load() bound it
-    assert _abi.ALL_PROTOTYPES["loc_impute_dose"] == want["loc_impute_dose"]
-    assert fn.restype is i and list(fn.argtypes) == want["loc_impute_dose"][1]
+    check_extension("impute", want, {"LOC_IMPUTE_STORE_RUN": 64})
 
 
 def test_a_later_header_that_declares_what_it_may_not_is_refused_by_name(tmp_path):
@@ -52,7 +40,7 @@ def test_a_later_header_that_declares_what_it_may_not_is_refused_by_name(tmp_pat
     assert run().returncode == 0
     path = tmp_path / "include" / "locator_hip_impute.h"
     text = path.read_text()
-    for addition, named in (("int loc_paint_copy(int N);", "loc_paint_copy"),       # a function of an EXTENSIONS header
+    for addition, named in (("int loc_paint_copy(int N);", "loc_paint_copy"),       # a function of an earlier header
                             ("int loc_version(void);", "loc_version"),              # a function of the main header
                             ("#define LOC_PAINT_TILE 2", "LOC_PAINT_TILE"),         # a constant outside its prefix
                             ("#define LOC_IMPUTE_TILE 2.5", "LOC_IMPUTE_TILE")):    # no integer

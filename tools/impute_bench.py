@@ -31,7 +31,7 @@ ABLATIONS = {1: "no cross-lane sums", 4: "no scratch rows", 8: "no dose stored",
 
 def bind(path):
     lib = C.CDLL(path)
-    for name, (res, args) in _abi.LATER["impute"].prototypes.items():
+    for name, (res, args) in _abi.EXTENSIONS["impute"].prototypes.items():
         getattr(lib, name).restype, getattr(lib, name).argtypes = res, args
     return lib
 
