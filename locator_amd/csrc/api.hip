@@ -5,7 +5,7 @@
 #include <stdio.h>
 
 #include "common.h"
-#include "stack_tail.h"
+#include "step_args.h"
 
 static thread_local char g_err[512] = "";
 
@@ -153,12 +153,15 @@ static int train_step_impl(const loc_net* net, const int32_t* rows, int n_b, int
     loc_param_layout(d, &lay);
     float *P = net->params, *M = net->adam_m, *V = net->adam_v;
     ws_view w = carve(d, net->ws, t_off & 1, slot, slot_cap_of(net));
+    const step_rows r = {net->X, net->x_pitch, rows, n_b};
+    const l1_state s1 = l1_state_of(P, M, V, lay);
+    const adam_clock clk = adam_clock_of(net, t_off);
     const int Hp = d->Hp, L = d->L, npre = d->n_pre;
     const int64_t blk = (int64_t)slot * Hp, HH = (int64_t)Hp * Hp;
     auto act = [&](int l) { return w.acts + (l - 1) * blk; };        // ELU output of layer l (1-based)
     auto dzl = [&](int l) { return w.dz + (l - 1) * blk; };          // dLoss/dz of layer l
     auto in_of = [&](int l) { return (use_drop && l - 1 == npre) ? w.adrop : act(l - 1); };  // input of layer l >= 2
-    const float* at = net->alpha_tab;
+    const float* at = net->alpha_tab;       // one by one for the per-layer launchers (stack_kernels.hip)
     const int atl = net->alpha_tab_len;
 
     // --nlayers 1: no hidden Dense layer, and the Dropout layer sits directly on the BatchNorm output (floor(1/2) = 0
@@ -179,24 +182,24 @@ static int train_step_impl(const loc_net* net, const int32_t* rows, int n_b, int
         }
     }
     if (!bn_ready)
-        TRY(loc_bn_batch_stats(net->X, net->x_pitch, rows, n_b, d->K, d->Kp, P + lay.gamma, P + lay.beta,
-                               P + lay.mov_mean, P + lay.mov_var, w.bn4, stream));
+        TRY(loc_bn_batch_stats(net->X, net->x_pitch, rows, n_b, d->K, d->Kp, s1.gamma, s1.beta, P + lay.mov_mean,
+                               P + lay.mov_var, w.bn4, stream));
     if (chain && fwd_done) {
         // the previous step's chained kernel left this minibatch's layer-1 partial sums: only add them up
         const bool dr = use_drop && npre == 1;
-        TRY(loc_l1_reduce_launch_drop(w.partial, chain_groups_of(net), 32 * chain_rb_of(net), Hp, P + lay.b1, act(1),
+        TRY(loc_l1_reduce_launch_drop(w.partial, chain_groups_of(net), 32 * chain_rb_of(net), Hp, s1.b1, act(1),
                                       dr ? w.adrop : nullptr, dr ? mask : nullptr, ks, stream));
     } else if (n_b > LOC_ROWS) {
         // large-M forward, exact fp32 products (3 bf16 pieces); fills whole 128-row tiles of the activation slot
-        TRY(loc_l1_forward_rows(net->X, net->x_pitch, rows, n_b, d, w.bn4, P + lay.w1, P + lay.b1, w.partial,
-                                w.partial_floats, act(1), 3, 0, &net->tune, stream));
+        TRY(loc_l1_forward_rows(net->X, net->x_pitch, rows, n_b, d, w.bn4, s1.w1s, s1.b1, w.partial, w.partial_floats,
+                                act(1), 3, 0, &net->tune, stream));
     } else if (in_drop) {
-        TRY(loc_l1_forward_in_dropout(net->X, net->x_pitch, rows, n_b, d, w.bn4, P + lay.w1, P + lay.b1, w.partial,
+        TRY(loc_l1_forward_in_dropout(net->X, net->x_pitch, rows, n_b, d, w.bn4, s1.w1s, s1.b1, w.partial,
                                       net->l1_fwd_grid, act(1), mask, ks, stream));
     } else {
         const bool dr = use_drop && npre == 1;
-        TRY(loc_l1_forward(net->X, net->x_pitch, rows, n_b, d, w.bn4, P + lay.w1, P + lay.b1, w.partial,
-                           net->l1_fwd_grid, act(1), dr ? w.adrop : nullptr, dr ? mask : nullptr, ks, stream));
+        TRY(loc_l1_forward(net->X, net->x_pitch, rows, n_b, d, w.bn4, s1.w1s, s1.b1, w.partial, net->l1_fwd_grid,
+                           act(1), dr ? w.adrop : nullptr, dr ? mask : nullptr, ks, stream));
     }
     if (fused) {
         // fused row-parallel hidden stack -> layer-1 backward -> ONE tail launch for everything that reduces over the
@@ -207,44 +210,32 @@ static int train_step_impl(const loc_net* net, const int32_t* rows, int n_b, int
                                        P + lay.bb, use_drop ? mask : nullptr, ks, Hp, L, npre, n_b, slot, rows, net->Y,
                                        w.acts, w.adrop, w.dz, w.head_out, &net->tune, stream));
         if (ev_l1b0) (void)hipEventRecord((hipEvent_t)ev_l1b0, (hipStream_t)stream);
+        const loc_dw_tail_args ta =
+            dw_tail_args_of(L, npre, n_b, slot, use_drop ? 1 : 0, w.acts, w.adrop, w.dz, w.head_out, P, M, V, net->wht, lay.wh,
+                            lay.bh, lay.wa, lay.ba, lay.wb, lay.bb, loss_out, clk);
         if (chain) {
             // layer-1 backward + Adam (W1, b1, gamma, beta, the next step's scale/shift) and -- rows_next given -- the
             // next minibatch's layer-1 forward partial sums from the weights while they are in registers
             // ... and, unless tune.chain_tail says otherwise, the step's hidden-layer / head Adam tail as trailing
             // workgroups of the same launch (it only needs what the stack kernel left in scratch)
             const bool merged = net->tune.chain_tail >= 0;
-            loc_dw_tail_args ta;
-            ta.L = L; ta.n_pre = npre; ta.n_b = n_b; ta.use_drop = use_drop ? 1 : 0;
-            ta.acts = w.acts; ta.adrop = w.adrop; ta.dz = w.dz; ta.head_out = w.head_out;
-            ta.P = P; ta.M = M; ta.V = V; ta.WhT = net->wht;
-            ta.off_wh = lay.wh; ta.off_bh = lay.bh; ta.off_wa = lay.wa; ta.off_ba = lay.ba; ta.off_wb = lay.wb; ta.off_bb = lay.bb;
-            ta.loss_out = loss_out; ta.alpha_tab = at; ta.alpha_tab_len = atl; ta.lr = net->lr; ta.t_base = net->t_base;
-            ta.t_off = t_off; ta.slot_rows = slot;
-            TRY(l1_chain_launch(net->X, net->x_pitch, rows, n_b, rows_next, n_b_next, d, w.bn4, bn_next_stats, dzl(1),
-                                P + lay.w1, M + lay.w1, V + lay.w1, P + lay.gamma, P + lay.beta, M + lay.gamma,
-                                V + lay.gamma, M + lay.beta, V + lay.beta, P + lay.b1, M + lay.b1, V + lay.b1, at, atl,
-                                net->lr, net->t_base, t_off, chain_grid_of(net), w.partial, w.partial_floats, &net->tune,
-                                merged ? &ta : nullptr, chain_rb_of(net), stream));
+            TRY(l1_chain_launch(r, rows_next, n_b_next, d, w.bn4, bn_next_stats, dzl(1), s1, clk, chain_grid_of(net),
+                                w.partial, w.partial_floats, &net->tune, merged ? &ta : nullptr, chain_rb_of(net), stream));
             if (ev_l1b1) (void)hipEventRecord((hipEvent_t)ev_l1b1, (hipStream_t)stream);
-            if (!merged)
-                TRY(loc_stack_dw_adam_tail(Hp, L, npre, n_b, slot, use_drop ? 1 : 0, w.acts, w.adrop, w.dz, w.head_out, P,
-                                           M, V, net->wht, lay.wh, lay.bh, lay.wa, lay.ba, lay.wb, lay.bb, loss_out, at,
-                                           atl, net->lr, net->t_base, t_off, nullptr, stream));
+            if (!merged) TRY(loc_stack_dw_adam_tail(Hp, ta, nullptr, stream));
             return 0;
         }
-        TRY(loc_l1_backward_adam_main(net->X, net->x_pitch, rows, n_b, d, w.bn4, dzl(1), P + lay.w1, M + lay.w1,
-                                      V + lay.w1, P + lay.b1, M + lay.b1, V + lay.b1, w.gbs, at, atl, net->lr,
-                                      net->t_base, t_off, net->l1_bwd_grid, &net->tune, stream));
+        // main kernel only: the gamma / beta update rides in the tail launch below
+        TRY(l1_backward_impl(r, d, w.bn4, dzl(1), s1, w.gbs, clk, net->l1_bwd_grid, &net->tune, nullptr, 1.f, nullptr,
+                             stream));
         if (ev_l1b1) (void)hipEventRecord((hipEvent_t)ev_l1b1, (hipStream_t)stream);
         loc_gb_tail gb;
         gb.K = d->K; gb.Kp = d->Kp; gb.gbs = w.gbs;
-        gb.gamma = P + lay.gamma; gb.beta = P + lay.beta;
-        gb.m_gamma = M + lay.gamma; gb.v_gamma = V + lay.gamma;
-        gb.m_beta = M + lay.beta; gb.v_beta = V + lay.beta;
+        gb.gamma = s1.gamma; gb.beta = s1.beta;
+        gb.m_gamma = s1.m_gamma; gb.v_gamma = s1.v_gamma;
+        gb.m_beta = s1.m_beta; gb.v_beta = s1.v_beta;
         gb.next_stats = bn_next_stats; gb.bn4 = w.bn4;
-        TRY(loc_stack_dw_adam_tail(Hp, L, npre, n_b, slot, use_drop ? 1 : 0, w.acts, w.adrop, w.dz, w.head_out, P, M, V,
-                                   net->wht, lay.wh, lay.bh, lay.wa, lay.ba, lay.wb, lay.bb, loss_out, at, atl, net->lr,
-                                   net->t_base, t_off, &gb, stream));
+        TRY(loc_stack_dw_adam_tail(Hp, ta, &gb, stream));
         return 0;
     }
     for (int l = 2; l <= L; ++l) {
@@ -273,19 +264,11 @@ static int train_step_impl(const loc_net* net, const int32_t* rows, int n_b, int
                                M + lay.wh, V + lay.wh, P + lay.bh, M + lay.bh, V + lay.bh, Hp, at, atl, net->lr,
                                net->t_base, t_off, stream));
     if (ev_l1b0) (void)hipEventRecord((hipEvent_t)ev_l1b0, (hipStream_t)stream);
-    if (in_drop) {
-        TRY(loc_l1_backward_adam_in_dropout(net->X, net->x_pitch, rows, n_b, d, w.bn4, dzl(1), P + lay.w1, M + lay.w1,
-                                            V + lay.w1, P + lay.gamma, P + lay.beta, M + lay.gamma, V + lay.gamma,
-                                            M + lay.beta, V + lay.beta, P + lay.b1, M + lay.b1, V + lay.b1, w.gbs, at,
-                                            atl, net->lr, net->t_base, t_off, net->l1_bwd_grid, bn_next_stats, w.bn4,
-                                            &net->tune, mask, ks, stream));
-        if (ev_l1b1) (void)hipEventRecord((hipEvent_t)ev_l1b1, (hipStream_t)stream);
-        return 0;
-    }
-    TRY(loc_l1_backward_adam(net->X, net->x_pitch, rows, n_b, d, w.bn4, dzl(1), P + lay.w1, M + lay.w1, V + lay.w1,
-                             P + lay.gamma, P + lay.beta, M + lay.gamma, V + lay.gamma, M + lay.beta, V + lay.beta,
-                             P + lay.b1, M + lay.b1, V + lay.b1, w.gbs, at, atl, net->lr, net->t_base, t_off,
-                             net->l1_bwd_grid, bn_next_stats, w.bn4, ev_l1b1, &net->tune, stream));
+    // --nlayers 1 with dropout: the keep mask goes into the kernel, and ev_l1b1 follows the gamma / beta update too
+    const l1_gb_stage gbu = {bn_next_stats, w.bn4, in_drop ? nullptr : ev_l1b1};
+    TRY(l1_backward_impl(r, d, w.bn4, dzl(1), s1, w.gbs, clk, net->l1_bwd_grid, &net->tune, in_drop ? mask : nullptr,
+                         in_drop ? ks : 1.f, &gbu, stream));
+    if (in_drop && ev_l1b1) (void)hipEventRecord((hipEvent_t)ev_l1b1, (hipStream_t)stream);
     return 0;
 }
 

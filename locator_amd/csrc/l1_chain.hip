@@ -47,7 +47,7 @@
 // sub-step.  dZ alone is 64 KB of LDS at this width, the kernel's 147 KB still fit one workgroup per compute unit.
 #include <type_traits>
 #include "common.h"
-#include "stack_tail.h"
+#include "step_args.h"
 
 // timing ablations (make ablate_chain A=<bits>): results are WRONG with any bit set; they only answer "what does this
 // part of the loop cost".  1 = no barrier, 2 = no per-tile small operands, 4 = no next-forward part, 16 = no Adam
@@ -549,14 +549,11 @@ bool l1_chain_offsets_fit(const loc_dims* d) { return (int64_t)d->Kp <= l1_chain
 // partial groups the chained kernel leaves per workgroup (k-tile slots a workgroup owns at a time)
 extern "C" int loc_l1_chain_groups_per_workgroup(int Hp) { return loc_l1_chain_supported(Hp) ? ch_ktw(Hp / 32) : 0; }
 
-int l1_chain_launch(const uint8_t* X, int64_t x_pitch, const int32_t* rows, int n_b,
-                                          const int32_t* rows_next, int n_b_next, const loc_dims* d, float* bn4,
-                                          const float* bn_next_stats, const float* dz1, float* w1s, float* m1s,
-                                          float* v1s, float* gamma, float* beta, float* m_gamma, float* v_gamma,
-                                          float* m_beta, float* v_beta, float* b1, float* m_b1, float* v_b1,
-                                          const float* alpha_tab, int alpha_tab_len, const float* lr, const int* t_base,
-                                          int t_off, int grid, float* partial, int64_t partial_floats,
-                                          const loc_tuning* tune, const loc_dw_tail_args* tail, int rb, void* stream) {
+int l1_chain_launch(const step_rows& r, const int32_t* rows_next, int n_b_next, const loc_dims* d, float* bn4,
+                    const float* bn_next_stats, const float* dz1, const l1_state& s, const adam_clock& c, int grid,
+                    float* partial, int64_t partial_floats, const loc_tuning* tune, const loc_dw_tail_args* tail, int rb,
+                    void* stream) {
+    const int n_b = r.n_b;
     // rb = 32-row blocks the kernel is built for (1, or 2 for --batch_size 33..64 at width 256): fixed for a fit, because
     // the partial sums it leaves are [group][32 rb][Hp]
     if (rb < 1 || rb > 2 || (rb == 2 && d->Hp != 256)) {
@@ -571,11 +568,11 @@ int l1_chain_launch(const uint8_t* X, int64_t x_pitch, const int32_t* rows, int 
                       max_rows, n_b_next);
         return -1;
     }
-    if ((x_pitch % 16) != 0 || ((uintptr_t)X % 16) != 0) {
-        loc_set_error("loc_l1_backward_adam_chain: genotype rows must be 16-byte aligned (pitch %lld)", (long long)x_pitch);
+    if ((r.x_pitch % 16) != 0 || ((uintptr_t)r.X % 16) != 0) {
+        loc_set_error("loc_l1_backward_adam_chain: genotype rows must be 16-byte aligned (pitch %lld)", (long long)r.x_pitch);
         return -1;
     }
-    if (beta != gamma + d->Kp || m_beta != m_gamma + d->Kp || v_beta != v_gamma + d->Kp) {
+    if (s.beta != s.gamma + d->Kp || s.m_beta != s.m_gamma + d->Kp || s.v_beta != s.v_gamma + d->Kp) {
         loc_set_error("loc_l1_backward_adam_chain: beta / m_beta / v_beta must sit Kp floats behind gamma / m_gamma / v_gamma "
                       "(loc_param_layout)");
         return -1;
@@ -609,10 +606,10 @@ int l1_chain_launch(const uint8_t* X, int64_t x_pitch, const int32_t* rows, int 
 #define LAUNCH_CHAIN_NR(M, N, R)                                                                                   \
     {                                                                                                              \
         LOC_ENSURE_LDS((l1_bwd_adam_chain_kernel<M, N, R>), lds);                                                  \
-        hipLaunchKernelGGL((l1_bwd_adam_chain_kernel<M, N, R>), dim3(grid + n_tail), dim3(512), lds, (hipStream_t)stream, X, \
-                           x_pitch, rows, n_b, rows_next, n_b_next, d->K, d->Kp, bn4, bn_next_stats, dz1, w1s, m1s, v1s, \
-                           gamma, beta, m_gamma, v_gamma, m_beta, v_beta, b1, m_b1, v_b1, alpha_tab, alpha_tab_len, lr, \
-                           t_base, t_off, partial, n_tail, ta);                                                    \
+        hipLaunchKernelGGL((l1_bwd_adam_chain_kernel<M, N, R>), dim3(grid + n_tail), dim3(512), lds, (hipStream_t)stream, r.X, \
+                           r.x_pitch, r.rows, n_b, rows_next, n_b_next, d->K, d->Kp, bn4, bn_next_stats, dz1, s.w1s, s.m1s, \
+                           s.v1s, s.gamma, s.beta, s.m_gamma, s.v_gamma, s.m_beta, s.v_beta, s.b1, s.m_b1, s.v_b1,   \
+                           c.alpha_tab, c.alpha_tab_len, c.lr, c.t_base, c.t_off, partial, n_tail, ta);            \
     }
 #define LAUNCH_CHAIN_N(M, N) LAUNCH_CHAIN_NR(M, N, 1)
 #define LAUNCH_CHAIN(M)                                                                                            \
@@ -651,7 +648,8 @@ extern "C" int loc_l1_backward_adam_chain(const uint8_t* X, int64_t x_pitch, con
                                           const float* alpha_tab, int alpha_tab_len, const float* lr, const int* t_base,
                                           int t_off, int grid, float* partial, int64_t partial_floats,
                                           const loc_tuning* tune, void* stream) {
-    return l1_chain_launch(X, x_pitch, rows, n_b, rows_next, n_b_next, d, bn4, bn_next_stats, dz1, w1s, m1s, v1s, gamma, beta,
-                           m_gamma, v_gamma, m_beta, v_beta, b1, m_b1, v_b1, alpha_tab, alpha_tab_len, lr, t_base, t_off,
-                           grid, partial, partial_floats, tune, nullptr, 1, stream);
+    return l1_chain_launch({X, x_pitch, rows, n_b}, rows_next, n_b_next, d, bn4, bn_next_stats, dz1,
+                           {w1s, m1s, v1s, gamma, beta, m_gamma, v_gamma, m_beta, v_beta, b1, m_b1, v_b1},
+                           {alpha_tab, alpha_tab_len, lr, t_base, t_off}, grid, partial, partial_floats, tune, nullptr, 1,
+                           stream);
 }

@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "step_args.h"
 
 #define LP 36  // LDS pitch (floats) of a [row][32 k] tile: 16-B aligned rows, conflict-free ds_read_b128
 
@@ -887,49 +888,19 @@ extern "C" int loc_bn_batch_stats(const uint8_t* X, int64_t x_pitch, const int32
     return 0;
 }
 
-extern "C" int loc_bn_epoch_stats(const uint8_t* X, int64_t x_pitch, const int32_t* rows_all, int batch, int n_last,
-                                  int n_steps, int K, int Kp, const float* gamma, const float* beta,
-                                  float* mov_mean, float* mov_var, float* stats_ep, float* bn4, void* stream) {
-    if (batch < 1 || batch > LOC_BIG_BATCH_MAX || n_last < 1 || n_last > batch || n_steps < 1) {
-        loc_set_error("loc_bn_epoch_stats: bad batch=%d n_last=%d n_steps=%d", batch, n_last, n_steps);
+// Batch statistics of every step of an epoch, then the n_steps moving-statistics updates (+ step 0's bn4 unless NULL); the
+// halves also stand alone, for an epoch whose first forward was chained into the previous epoch's last step.  unit: the
+// fixed-point unit of X (--dosage: statistics in q units with the compensated variance; 1 = the GT
+// kernel).  who: the entry point; one without a unit argument passes 1 and leaves it out of the refusal (unit_form false)
+static int bn_epoch_stats_unit_launch(const char* who, bool unit_form, const uint8_t* X, int64_t x_pitch,
+                                      const int32_t* rows_all, int batch, int n_last, int n_steps, int K, int Kp,
+                                      float* stats_ep, int unit, void* stream) {
+    if (batch < 1 || batch > LOC_BIG_BATCH_MAX || n_last < 1 || n_last > batch || n_steps < 1 || unit < 1 ||
+        unit > LOC_DOSAGE_UNIT) {
+        if (unit_form) loc_set_error("%s: bad batch=%d n_last=%d n_steps=%d unit=%d", who, batch, n_last, n_steps, unit);
+        else loc_set_error("%s: bad batch=%d n_last=%d n_steps=%d", who, batch, n_last, n_steps);
         return -1;
     }
-    hipLaunchKernelGGL(bn_epoch_stats_kernel<false>, dim3((Kp / 4 + 127) / 128, n_steps), dim3(128), 0, (hipStream_t)stream,
-                       X, x_pitch, rows_all, batch, n_last, n_steps, K, Kp, stats_ep, 0.f);
-    LOC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bn_epoch_finish_kernel, dim3((Kp + 255) / 256), dim3(256), 0, (hipStream_t)stream, K, Kp,
-                       n_steps, stats_ep, gamma, beta, mov_mean, mov_var, bn4);
-    LOC_CHECK_LAUNCH();
-    return 0;
-}
-
-// The two halves on their own (round 4: an epoch whose first layer-1 forward was chained into the previous epoch's last
-// step computes the NEXT epoch's batch statistics early and applies its own moving-statistics updates without touching
-// the scale / shift the chained kernel left): stats only, then the n_steps moving updates (+ step 0's bn4 unless NULL).
-extern "C" int loc_bn_epoch_stats_only(const uint8_t* X, int64_t x_pitch, const int32_t* rows_all, int batch, int n_last,
-                                       int n_steps, int K, int Kp, float* stats_ep, void* stream) {
-    if (batch < 1 || batch > LOC_BIG_BATCH_MAX || n_last < 1 || n_last > batch || n_steps < 1) {
-        loc_set_error("loc_bn_epoch_stats_only: bad batch=%d n_last=%d n_steps=%d", batch, n_last, n_steps);
-        return -1;
-    }
-    hipLaunchKernelGGL(bn_epoch_stats_kernel<false>, dim3((Kp / 4 + 127) / 128, n_steps), dim3(128), 0, (hipStream_t)stream,
-                       X, x_pitch, rows_all, batch, n_last, n_steps, K, Kp, stats_ep, 0.f);
-    LOC_CHECK_LAUNCH();
-    return 0;
-}
-extern "C" int loc_bn_epoch_finish(int n_steps, int K, int Kp, const float* gamma, const float* beta, float* mov_mean,
-                                   float* mov_var, const float* stats_ep, float* bn4, void* stream) {
-    if (n_steps < 1) { loc_set_error("loc_bn_epoch_finish: n_steps=%d", n_steps); return -1; }
-    hipLaunchKernelGGL(bn_epoch_finish_kernel, dim3((Kp + 255) / 256), dim3(256), 0, (hipStream_t)stream, K, Kp,
-                       n_steps, stats_ep, gamma, beta, mov_mean, mov_var, bn4);
-    LOC_CHECK_LAUNCH();
-    return 0;
-}
-
-// --dosage forms of the two entry points above (trailing argument: the fixed-point unit of X, LOC_DOSAGE_UNIT; 1 = the GT
-// kernels themselves).  Moving statistics and bn4 then run in q units with the compensated variance.
-static int bn_epoch_stats_unit_launch(const uint8_t* X, int64_t x_pitch, const int32_t* rows_all, int batch, int n_last,
-                                      int n_steps, int K, int Kp, float* stats_ep, int unit, void* stream) {
     if (unit == 1) {
         hipLaunchKernelGGL(bn_epoch_stats_kernel<false>, dim3((Kp / 4 + 127) / 128, n_steps), dim3(128), 0, (hipStream_t)stream,
                            X, x_pitch, rows_all, batch, n_last, n_steps, K, Kp, stats_ep, 0.f);
@@ -940,31 +911,42 @@ static int bn_epoch_stats_unit_launch(const uint8_t* X, int64_t x_pitch, const i
     LOC_CHECK_LAUNCH();
     return 0;
 }
-
-static bool bn_unit_ok(int unit) { return unit >= 1 && unit <= LOC_DOSAGE_UNIT; }
-
-extern "C" int loc_bn_epoch_stats_unit(const uint8_t* X, int64_t x_pitch, const int32_t* rows_all, int batch, int n_last,
-                                       int n_steps, int K, int Kp, const float* gamma, const float* beta,
-                                       float* mov_mean, float* mov_var, float* stats_ep, float* bn4, int unit, void* stream) {
-    if (batch < 1 || batch > LOC_BIG_BATCH_MAX || n_last < 1 || n_last > batch || n_steps < 1 || !bn_unit_ok(unit)) {
-        loc_set_error("loc_bn_epoch_stats_unit: bad batch=%d n_last=%d n_steps=%d unit=%d", batch, n_last, n_steps, unit);
-        return -1;
-    }
-    int rc = bn_epoch_stats_unit_launch(X, x_pitch, rows_all, batch, n_last, n_steps, K, Kp, stats_ep, unit, stream);
-    if (rc) return rc;
+static int bn_epoch_finish_launch(int n_steps, int K, int Kp, const float* gamma, const float* beta, float* mov_mean,
+                                  float* mov_var, const float* stats_ep, float* bn4, void* stream) {
     hipLaunchKernelGGL(bn_epoch_finish_kernel, dim3((Kp + 255) / 256), dim3(256), 0, (hipStream_t)stream, K, Kp,
                        n_steps, stats_ep, gamma, beta, mov_mean, mov_var, bn4);
     LOC_CHECK_LAUNCH();
     return 0;
 }
 
+extern "C" int loc_bn_epoch_stats_unit(const uint8_t* X, int64_t x_pitch, const int32_t* rows_all, int batch, int n_last,
+                                       int n_steps, int K, int Kp, const float* gamma, const float* beta,
+                                       float* mov_mean, float* mov_var, float* stats_ep, float* bn4, int unit, void* stream) {
+    int rc = bn_epoch_stats_unit_launch("loc_bn_epoch_stats_unit", true, X, x_pitch, rows_all, batch, n_last, n_steps, K, Kp,
+                                        stats_ep, unit, stream);
+    return rc ? rc : bn_epoch_finish_launch(n_steps, K, Kp, gamma, beta, mov_mean, mov_var, stats_ep, bn4, stream);
+}
+extern "C" int loc_bn_epoch_stats(const uint8_t* X, int64_t x_pitch, const int32_t* rows_all, int batch, int n_last,
+                                  int n_steps, int K, int Kp, const float* gamma, const float* beta,
+                                  float* mov_mean, float* mov_var, float* stats_ep, float* bn4, void* stream) {
+    int rc = bn_epoch_stats_unit_launch("loc_bn_epoch_stats", false, X, x_pitch, rows_all, batch, n_last, n_steps, K, Kp,
+                                        stats_ep, 1, stream);
+    return rc ? rc : bn_epoch_finish_launch(n_steps, K, Kp, gamma, beta, mov_mean, mov_var, stats_ep, bn4, stream);
+}
 extern "C" int loc_bn_epoch_stats_only_unit(const uint8_t* X, int64_t x_pitch, const int32_t* rows_all, int batch, int n_last,
                                             int n_steps, int K, int Kp, float* stats_ep, int unit, void* stream) {
-    if (batch < 1 || batch > LOC_BIG_BATCH_MAX || n_last < 1 || n_last > batch || n_steps < 1 || !bn_unit_ok(unit)) {
-        loc_set_error("loc_bn_epoch_stats_only_unit: bad batch=%d n_last=%d n_steps=%d unit=%d", batch, n_last, n_steps, unit);
-        return -1;
-    }
-    return bn_epoch_stats_unit_launch(X, x_pitch, rows_all, batch, n_last, n_steps, K, Kp, stats_ep, unit, stream);
+    return bn_epoch_stats_unit_launch("loc_bn_epoch_stats_only_unit", true, X, x_pitch, rows_all, batch, n_last, n_steps, K,
+                                      Kp, stats_ep, unit, stream);
+}
+extern "C" int loc_bn_epoch_stats_only(const uint8_t* X, int64_t x_pitch, const int32_t* rows_all, int batch, int n_last,
+                                       int n_steps, int K, int Kp, float* stats_ep, void* stream) {
+    return bn_epoch_stats_unit_launch("loc_bn_epoch_stats_only", false, X, x_pitch, rows_all, batch, n_last, n_steps, K, Kp,
+                                      stats_ep, 1, stream);
+}
+extern "C" int loc_bn_epoch_finish(int n_steps, int K, int Kp, const float* gamma, const float* beta, float* mov_mean,
+                                   float* mov_var, const float* stats_ep, float* bn4, void* stream) {
+    if (n_steps < 1) { loc_set_error("loc_bn_epoch_finish: n_steps=%d", n_steps); return -1; }
+    return bn_epoch_finish_launch(n_steps, K, Kp, gamma, beta, mov_mean, mov_var, stats_ep, bn4, stream);
 }
 
 extern "C" float loc_bn_var_add(int unit) { return (float)(unit * unit - 1) * BN_EPS; }
@@ -977,11 +959,10 @@ extern "C" int loc_bn_infer_scale_shift(int K, int Kp, const float* gamma, const
     return 0;
 }
 
-static int l1_forward_impl(const uint8_t* X, int64_t x_pitch, const int32_t* rows, int n_b, const loc_dims* d,
-                           const float* scale_shift, const float* w1s, const float* b1, float* partial, int grid,
-                           float* a1, float* a1_drop, const uint8_t* mask, float keep_scale, const uint8_t* in_mask,
-                           float in_ks, void* stream) {
-    if (n_b < 1 || n_b > LOC_ROWS) { loc_set_error("loc_l1_forward: n_b=%d out of 1..32", n_b); return -1; }
+static int l1_forward_impl(const step_rows& r, const loc_dims* d, const float* scale_shift, const float* w1s,
+                           const float* b1, float* partial, int grid, float* a1, float* a1_drop, const uint8_t* mask,
+                           float keep_scale, const uint8_t* in_mask, float in_ks, void* stream) {
+    if (r.n_b < 1 || r.n_b > LOC_ROWS) { loc_set_error("loc_l1_forward: n_b=%d out of 1..32", r.n_b); return -1; }
     const int nkt = d->Kp / KT, nht = d->Hp / 32;
     if (grid < 1) grid = 1;
     if (grid > nkt) grid = nkt;
@@ -990,29 +971,26 @@ static int l1_forward_impl(const uint8_t* X, int64_t x_pitch, const int32_t* row
 #define LAUNCH_FWD(N)                                                                                      \
     {                                                                                                      \
         LOC_ENSURE_LDS((l1_fwd_partial_kernel<N>), lds);                                                   \
-        hipLaunchKernelGGL(l1_fwd_partial_kernel<N>, dim3(grid), dim3(512), lds, (hipStream_t)stream, X,   \
-                           x_pitch, rows, n_b, d->Kp, scale_shift, w1s, partial, in_mask, in_ks);          \
+        hipLaunchKernelGGL(l1_fwd_partial_kernel<N>, dim3(grid), dim3(512), lds, (hipStream_t)stream, r.X, \
+                           r.x_pitch, r.rows, r.n_b, d->Kp, scale_shift, w1s, partial, in_mask, in_ks);    \
     }
     NHT_SWITCH(nht, LAUNCH_FWD)
 #undef LAUNCH_FWD
     LOC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(l1_reduce_kernel, dim3(32 * d->Hp / 64), dim3(256), 0, (hipStream_t)stream, partial, grid,
-                       32, d->Hp, b1, a1, a1_drop, mask, keep_scale);
-    LOC_CHECK_LAUNCH();
-    return 0;
+    return loc_l1_reduce_launch_drop(partial, grid, 32, d->Hp, b1, a1, a1_drop, mask, keep_scale, stream);
 }
 
 extern "C" int loc_l1_forward(const uint8_t* X, int64_t x_pitch, const int32_t* rows, int n_b, const loc_dims* d,
                               const float* scale_shift, const float* w1s, const float* b1, float* partial, int grid,
                               float* a1, float* a1_drop, const uint8_t* mask, float keep_scale, void* stream) {
-    return l1_forward_impl(X, x_pitch, rows, n_b, d, scale_shift, w1s, b1, partial, grid, a1, a1_drop, mask, keep_scale,
+    return l1_forward_impl({X, x_pitch, rows, n_b}, d, scale_shift, w1s, b1, partial, grid, a1, a1_drop, mask, keep_scale,
                            nullptr, 1.f, stream);
 }
 extern "C" int loc_l1_forward_in_dropout(const uint8_t* X, int64_t x_pitch, const int32_t* rows, int n_b,
                                          const loc_dims* d, const float* scale_shift, const float* w1s, const float* b1,
                                          float* partial, int grid, float* a1, const uint8_t* in_mask, float keep_scale,
                                          void* stream) {
-    return l1_forward_impl(X, x_pitch, rows, n_b, d, scale_shift, w1s, b1, partial, grid, a1, nullptr, nullptr, 1.f,
+    return l1_forward_impl({X, x_pitch, rows, n_b}, d, scale_shift, w1s, b1, partial, grid, a1, nullptr, nullptr, 1.f,
                            in_mask, keep_scale, stream);
 }
 
@@ -1028,27 +1006,22 @@ int loc_l1_reduce_launch_drop(const float* partial, int G, int rows_p, int Hp, c
 
 // reduction of the large-M forward (l1_rows.hip): rows_p rows, no dropout
 int loc_l1_reduce_launch(const float* partial, int G, int rows_p, int Hp, const float* b1, float* a1, void* stream) {
-    hipLaunchKernelGGL(l1_reduce_kernel, dim3(rows_p * Hp / 64), dim3(256), 0, (hipStream_t)stream, partial, G,
-                       rows_p, Hp, b1, a1, (float*)nullptr, (const uint8_t*)nullptr, 1.f);
-    LOC_CHECK_LAUNCH();
-    return 0;
+    return loc_l1_reduce_launch_drop(partial, G, rows_p, Hp, b1, a1, nullptr, nullptr, 1.f, stream);
 }
 
 // main kernel only (W1 / b1); the gamma/beta update that consumes gb_scratch is launched by the caller
-static int l1_backward_main_impl(const uint8_t* X, int64_t x_pitch, const int32_t* rows, int n_b,
-                                 const loc_dims* d, const float* bn4, const float* dz1, float* w1s,
-                                 float* m1s, float* v1s, float* b1, float* m_b1, float* v_b1,
-                                 float* gb_scratch, const float* alpha_tab, int alpha_tab_len,
-                                 const float* lr, const int* t_base, int t_off, int grid,
+static int l1_backward_main_impl(const step_rows& r, const loc_dims* d, const float* bn4, const float* dz1,
+                                 const l1_state& s, float* gb_scratch, const adam_clock& c, int grid,
                                  const loc_tuning* tune, const uint8_t* in_mask, float in_ks, void* stream) {
+    const int n_b = r.n_b;
     // every form of the backward kernel takes the same arguments (the 32-row kernel two more: the Dropout mask on the
     // BatchNorm output and its scale); KERN in parentheses, since it holds template commas
 #define L1B_LAUNCH(KERN, GRID, BLOCK, LDS, ...)                                                                       \
     {                                                                                                                 \
         LOC_ENSURE_LDS(KERN, LDS);                                                                                    \
-        hipLaunchKernelGGL(KERN, dim3(GRID), dim3(BLOCK), LDS, (hipStream_t)stream, X, x_pitch, rows, n_b, d->K,      \
-                           d->Kp, bn4, dz1, w1s, m1s, v1s, gb_scratch, b1, m_b1, v_b1, alpha_tab, alpha_tab_len, lr,  \
-                           t_base, t_off, n_active, ##__VA_ARGS__);                                                   \
+        hipLaunchKernelGGL(KERN, dim3(GRID), dim3(BLOCK), LDS, (hipStream_t)stream, r.X, r.x_pitch, r.rows, n_b,      \
+                           d->K, d->Kp, bn4, dz1, s.w1s, s.m1s, s.v1s, gb_scratch, s.b1, s.m_b1, s.v_b1, c.alpha_tab, \
+                           c.alpha_tab_len, c.lr, c.t_base, c.t_off, n_active, ##__VA_ARGS__);                        \
     }
     if (in_mask && n_b > LOC_ROWS) {
         loc_set_error("loc_l1_backward_adam: dropout on the BatchNorm output (--nlayers 1) needs --batch_size <= 32");
@@ -1066,7 +1039,6 @@ static int l1_backward_main_impl(const uint8_t* X, int64_t x_pitch, const int32_
     grid = (n_active + 3) / 4;
     if (n_b > LOC_MAX_BATCH) {
         // more than 128 rows: row blocks streamed from L2 (l1_bwd_adam_big_kernel)
-        if (in_mask) { loc_set_error("loc_l1_backward_adam: --nlayers 1 with dropout needs --batch_size <= 32"); return -1; }
         const size_t lds_big = ((size_t)d->Hp + (size_t)(n_b + 31) / 32 * 32) * sizeof(float);
         switch (nht) {
             case 2: L1B_LAUNCH((l1_bwd_adam_big_kernel<2, 13>), grid, 256, lds_big) break;
@@ -1136,33 +1108,29 @@ static int l1_backward_main_impl(const uint8_t* X, int64_t x_pitch, const int32_
     return 0;
 }
 
+// main kernel, then (gb given) the gamma / beta update from gb_scratch: step_args.h
+int l1_backward_impl(const step_rows& r, const loc_dims* d, const float* bn4, const float* dz1, const l1_state& s,
+                     float* gb_scratch, const adam_clock& c, int grid, const loc_tuning* tune, const uint8_t* in_mask,
+                     float in_ks, const l1_gb_stage* gb, void* stream) {
+    int rc = l1_backward_main_impl(r, d, bn4, dz1, s, gb_scratch, c, grid, tune, in_mask, in_ks, stream);
+    if (rc || !gb) return rc;
+    if (gb->ev_after_main) (void)hipEventRecord((hipEvent_t)gb->ev_after_main, (hipStream_t)stream);
+    hipLaunchKernelGGL(l1_gamma_beta_adam_kernel, dim3((d->K + 255) / 256), dim3(256), 0, (hipStream_t)stream, d->K,
+                       gb_scratch, s.gamma, s.beta, s.m_gamma, s.v_gamma, s.m_beta, s.v_beta, c.alpha_tab, c.alpha_tab_len,
+                       c.lr, c.t_base, c.t_off, d->Kp, gb->bn_next_stats, gb->bn4_out);
+    LOC_CHECK_LAUNCH();
+    return 0;
+}
+
 extern "C" int loc_l1_backward_adam_main(const uint8_t* X, int64_t x_pitch, const int32_t* rows, int n_b,
                                          const loc_dims* d, const float* bn4, const float* dz1, float* w1s,
                                          float* m1s, float* v1s, float* b1, float* m_b1, float* v_b1,
                                          float* gb_scratch, const float* alpha_tab, int alpha_tab_len,
                                          const float* lr, const int* t_base, int t_off, int grid,
                                          const loc_tuning* tune, void* stream) {
-    return l1_backward_main_impl(X, x_pitch, rows, n_b, d, bn4, dz1, w1s, m1s, v1s, b1, m_b1, v_b1, gb_scratch, alpha_tab,
-                                 alpha_tab_len, lr, t_base, t_off, grid, tune, nullptr, 1.f, stream);
-}
-
-static int l1_backward_impl(const uint8_t* X, int64_t x_pitch, const int32_t* rows, int n_b,
-                            const loc_dims* d, const float* bn4, const float* dz1, float* w1s, float* m1s,
-                            float* v1s, float* gamma, float* beta, float* m_gamma, float* v_gamma,
-                            float* m_beta, float* v_beta, float* b1, float* m_b1, float* v_b1,
-                            float* gb_scratch, const float* alpha_tab, int alpha_tab_len, const float* lr,
-                            const int* t_base, int t_off, int grid, const float* bn_next_stats,
-                            float* bn4_out, void* ev_after_main, const loc_tuning* tune, const uint8_t* in_mask,
-                            float in_ks, void* stream) {
-    int rc = l1_backward_main_impl(X, x_pitch, rows, n_b, d, bn4, dz1, w1s, m1s, v1s, b1, m_b1, v_b1, gb_scratch,
-                                   alpha_tab, alpha_tab_len, lr, t_base, t_off, grid, tune, in_mask, in_ks, stream);
-    if (rc) return rc;
-    if (ev_after_main) (void)hipEventRecord((hipEvent_t)ev_after_main, (hipStream_t)stream);
-    hipLaunchKernelGGL(l1_gamma_beta_adam_kernel, dim3((d->K + 255) / 256), dim3(256), 0, (hipStream_t)stream, d->K,
-                       gb_scratch, gamma, beta, m_gamma, v_gamma, m_beta, v_beta, alpha_tab, alpha_tab_len, lr,
-                       t_base, t_off, d->Kp, bn_next_stats, bn4_out);
-    LOC_CHECK_LAUNCH();
-    return 0;
+    const l1_state s = {w1s, m1s, v1s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, b1, m_b1, v_b1};   // no gamma / beta
+    return l1_backward_main_impl({X, x_pitch, rows, n_b}, d, bn4, dz1, s, gb_scratch,
+                                 {alpha_tab, alpha_tab_len, lr, t_base, t_off}, grid, tune, nullptr, 1.f, stream);
 }
 
 extern "C" int loc_l1_backward_adam_in_dropout(const uint8_t* X, int64_t x_pitch, const int32_t* rows, int n_b,
@@ -1174,9 +1142,10 @@ extern "C" int loc_l1_backward_adam_in_dropout(const uint8_t* X, int64_t x_pitch
                                                int grid, const float* bn_next_stats, float* bn4_out,
                                                const loc_tuning* tune, const uint8_t* in_mask, float keep_scale,
                                                void* stream) {
-    return l1_backward_impl(X, x_pitch, rows, n_b, d, bn4, dz1, w1s, m1s, v1s, gamma, beta, m_gamma, v_gamma, m_beta,
-                            v_beta, b1, m_b1, v_b1, gb_scratch, alpha_tab, alpha_tab_len, lr, t_base, t_off, grid,
-                            bn_next_stats, bn4_out, nullptr, tune, in_mask, keep_scale, stream);
+    const l1_gb_stage gb = {bn_next_stats, bn4_out, nullptr};
+    return l1_backward_impl({X, x_pitch, rows, n_b}, d, bn4, dz1,
+                            {w1s, m1s, v1s, gamma, beta, m_gamma, v_gamma, m_beta, v_beta, b1, m_b1, v_b1}, gb_scratch,
+                            {alpha_tab, alpha_tab_len, lr, t_base, t_off}, grid, tune, in_mask, keep_scale, &gb, stream);
 }
 
 extern "C" int loc_l1_backward_adam(const uint8_t* X, int64_t x_pitch, const int32_t* rows, int n_b,
@@ -1186,7 +1155,8 @@ extern "C" int loc_l1_backward_adam(const uint8_t* X, int64_t x_pitch, const int
                                     float* gb_scratch, const float* alpha_tab, int alpha_tab_len, const float* lr,
                                     const int* t_base, int t_off, int grid, const float* bn_next_stats,
                                     float* bn4_out, void* ev_after_main, const loc_tuning* tune, void* stream) {
-    return l1_backward_impl(X, x_pitch, rows, n_b, d, bn4, dz1, w1s, m1s, v1s, gamma, beta, m_gamma, v_gamma, m_beta,
-                            v_beta, b1, m_b1, v_b1, gb_scratch, alpha_tab, alpha_tab_len, lr, t_base, t_off, grid,
-                            bn_next_stats, bn4_out, ev_after_main, tune, nullptr, 1.f, stream);
+    const l1_gb_stage gb = {bn_next_stats, bn4_out, ev_after_main};
+    return l1_backward_impl({X, x_pitch, rows, n_b}, d, bn4, dz1,
+                            {w1s, m1s, v1s, gamma, beta, m_gamma, v_gamma, m_beta, v_beta, b1, m_b1, v_b1}, gb_scratch,
+                            {alpha_tab, alpha_tab_len, lr, t_base, t_off}, grid, tune, nullptr, 1.f, &gb, stream);
 }

@@ -18,14 +18,7 @@ struct loc_dw_tail_args {
     int t_off, slot_rows;
 };
 
-// l1_chain.hip: loc_l1_backward_adam_chain with the tail above as trailing workgroups of the same launch (tail may be NULL)
-int l1_chain_launch(const uint8_t* X, int64_t x_pitch, const int32_t* rows, int n_b, const int32_t* rows_next, int n_b_next,
-                    const loc_dims* d, float* bn4, const float* bn_next_stats, const float* dz1, float* w1s, float* m1s,
-                    float* v1s, float* gamma, float* beta, float* m_gamma, float* v_gamma, float* m_beta, float* v_beta,
-                    float* b1, float* m_b1, float* v_b1, const float* alpha_tab, int alpha_tab_len, const float* lr,
-                    const int* t_base, int t_off, int grid, float* partial, int64_t partial_floats, const loc_tuning* tune,
-                    const loc_dw_tail_args* tail, int rb, void* stream);
-// l1_chain.hip: the chained kernel addresses W1 / m / v through 32-bit byte offsets, Kp * max(Hp, 256) * 4 < 2^32 (largest
+// l1_chain.hip (its launcher, l1_chain_launch, is declared in step_args.h): the chained kernel addresses W1 / m / v through 32-bit byte offsets, Kp * max(Hp, 256) * 4 < 2^32 (largest
 // padded SNP count 4,194,272 at widths 64..256, 2,097,120 at width 512); both the launcher and loc_train_chain_supported ask
 int64_t l1_chain_max_kp(int Hp);
 bool l1_chain_offsets_fit(const loc_dims* d);
