@@ -241,7 +241,8 @@ def read_inputs_sites(a, prog, phase=False):
 def refuse_unphased(n, where, prog):
     """The refusal of n heterozygous calls without phase (n None or 0: none is known of)."""
     if n:
-        raise SystemExit(f"{prog}: {where} has {n} heterozygous call(s) without phase (written 'a/b'); phase them first")
+        raise SystemExit(f"{prog}: {where} has {n} heterozygous call(s) without phase (written 'a/b'); phase them first (python -m "
+                         "locator_amd.phase)")
 
 
 def read_locations(sample_data, samples, prog):

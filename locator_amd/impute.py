@@ -43,7 +43,8 @@ device's round-off).  The device computes in fp32 (loc_impute_dose, include/loca
 agree within round-off; each path is deterministic.  --budget_gb bounds the scratch and the dose rows of one launch (the
 recipients go in batches, which changes no bit).
 
-Not built: recombination maps, per-population donor pools, ploidy other than 2, phasing, writing a VCF.
+Not built: recombination maps, per-population donor pools, ploidy other than 2, writing a VCF.  Unphased calls are phased by
+`python -m locator_amd.phase` first.
 """
 from __future__ import annotations
 
@@ -104,26 +105,32 @@ def dose_device(h, donor, owner, rec, rho, theta, block=0, pitch=None, pad_fill=
 
 # ---------------------------------------------------------------- the command's pieces
 
-def read_phased(path, zarr):
+def read_phased(path, zarr, prog=PROG, refuse=True):
     """{gt (V, N, P) int8, samples, chrom, pos, ref, alt (the first ALT)} of a phased VCF (zarr False) or zarr store, after the
-    refusal of heterozygous calls without phase and of a store without the variants' tables."""
+    refusal of heterozygous calls without phase and of a store without the variants' tables.  refuse False (the phase command,
+    under its own name `prog`): such calls are counted into the entry unphased_hets instead (0: none is known of)."""
     from . import genotypes as G
     if zarr:
         callset = G.open_group(path, mode="r")
-        B.refuse_unphased(G.zarr_unphased_hets(callset), f"{path}: calldata/GT_phased", PROG)
+        unphased = G.zarr_unphased_hets(callset)
+        if refuse:
+            B.refuse_unphased(unphased, f"{path}: calldata/GT_phased", prog)
         try:
             d = G.zarr_sites(callset)
         except KeyError as e:
-            raise SystemExit(f"{PROG}: {path} lacks {e.args[0]}: sites are identified by CHROM, POS, REF and ALT") from None
+            raise SystemExit(f"{prog}: {path} lacks {e.args[0]}: sites are identified by CHROM, POS, REF and ALT") from None
         d["calldata/GT"], d["samples"] = np.asarray(callset["calldata/GT"][:], dtype=np.int8), np.asarray(callset["samples"][:])
     else:
         d = G.read_vcf(path, phase=True, sites=True)
-        B.refuse_unphased(d["unphased_hets"], path, PROG)
+        unphased = d["unphased_hets"]
+        if refuse:
+            B.refuse_unphased(unphased, path, prog)
     gt = np.asarray(d["calldata/GT"], dtype=np.int8)
     if gt.ndim != 3 or gt.shape[2] != 2:
-        raise SystemExit(f"{PROG}: {path}: calls of ploidy {gt.shape[2] if gt.ndim == 3 else '?'}: the copying model is built for two "
+        raise SystemExit(f"{prog}: {path}: calls of ploidy {gt.shape[2] if gt.ndim == 3 else '?'}: the copying model is built for two "
                          "haplotypes a sample")
-    return {"gt": gt, "samples": np.asarray(d["samples"]).astype(str), **G.site_columns(d)}
+    tables = {"gt": gt, "samples": np.asarray(d["samples"]).astype(str), **G.site_columns(d)}
+    return tables if refuse else {**tables, "unphased_hets": int(unphased or 0)}
 
 
 def biallelic(d):

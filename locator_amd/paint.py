@@ -49,7 +49,8 @@ include/locator_hip_paint.h): the files of the two paths agree within round-off 
 deterministic.  --host_dtype float32 runs the NumPy form in float32, the yardstick the device's round-off is measured against;
 --budget_gb bounds the scratch of one launch (the recipients go in batches, which changes no bit).
 
-Not built: recombination maps, per-population donor pools, ploidy other than 2, estimating theta.
+Not built: recombination maps, per-population donor pools, ploidy other than 2, estimating theta.  Unphased calls are phased by
+`python -m locator_amd.phase` first.
 """
 from __future__ import annotations
 
