@@ -2,7 +2,8 @@
 structs as ctypes Structures (STRUCTS) and the prototypes as (restype, argtypes) pairs (PROTOTYPES).  Nothing else in the
 package restates the header.  The headers of the later entry points (_EXTENSION_TABLE: one line a header) are read likewise:
 EXTENSIONS[tag] holds a header's path, constants and prototypes, the constants are module attributes too, and ALL_PROTOTYPES
-is what the library binds.  _LATER_TABLE -> LATER[tag] is the same for the headers added since EXTENSIONS' tags were pinned.  No torch here: locator_amd.genotypes and the command line import this module before torch.
+is what the library binds.  _LATER_TABLE -> LATER[tag] is the same for the headers added since EXTENSIONS' tags were pinned, and _OPEN_TABLE -> OPEN[tag]
+for those added since LATER's were.  No torch here: locator_amd.genotypes and the command line import this module before torch.
 
 The reader knows the header's spelling, not C: one declaration per `;`, scalar types from _SCALARS, comments only as
 /* */.  Anything else raises with the offending text, so that a header edit cannot silently drop or mis-type an entry."""
@@ -29,9 +30,15 @@ _EXTENSION_TABLE = (
     ("impute", "locator_hip_impute.h", "LOC_IMPUTE_"),
 )
 # The headers added after that table's tags were pinned (tests/abi_util.py states them and is a yardstick that later changes leave
-# alone), in the same form, read by the same loop with the same refusals: LATER[tag].  A new header goes here.
+# alone), in the same form, read by the same loop with the same refusals: LATER[tag].  Its tags are pinned too (tests/test_phase.py).
 _LATER_TABLE = (
     ("phase", "locator_hip_phase.h", "LOC_PHASE_"),
+)
+# The open table, in the same form, read by the same loop with the same refusals: OPEN[tag].  New headers go here, at the end.  A
+# test asserts only the line of its own tag (OPEN["local"]), never the list of this table's keys, so that the next header needs no
+# fourth table.
+_OPEN_TABLE = (
+    ("local", "locator_hip_local.h", "LOC_LOCAL_"),
 )
 
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
@@ -123,10 +130,10 @@ class Extension(NamedTuple):
     prototypes: dict
 
 
-EXTENSIONS, LATER = {}, {}
+EXTENSIONS, LATER, OPEN = {}, {}, {}
 ALL_PROTOTYPES = dict(PROTOTYPES)
 _declared = set(CONSTANTS) | set(PROTOTYPES)         # by the main header and the tables' lines so far
-for _into, _table in ((EXTENSIONS, _EXTENSION_TABLE), (LATER, _LATER_TABLE)):
+for _into, _table in ((EXTENSIONS, _EXTENSION_TABLE), (LATER, _LATER_TABLE), (OPEN, _OPEN_TABLE)):
     for _tag, _name, _prefix in _table:
         _path = os.path.join(os.path.dirname(HEADER), _name)
         if not os.path.exists(_path):
@@ -135,7 +142,7 @@ for _into, _table in ((EXTENSIONS, _EXTENSION_TABLE), (LATER, _LATER_TABLE)):
             _consts, _structs, _protos = parse(_f.read())
         _again = sorted(_declared & (set(_consts) | set(_protos)))
         _foreign = sorted(k for k, v in _consts.items() if _prefix is None or not k.startswith(_prefix) or not isinstance(v, int))
-        if _structs or _again or _foreign or _tag in EXTENSIONS or _tag in LATER:
+        if _structs or _again or _foreign or _tag in EXTENSIONS or _tag in LATER or _tag in OPEN:
             raise ValueError(f"{_path} may declare new functions " + ("only" if _prefix is None else f"and {_prefix}* integer constants only")
                              + "".join(f"; {what}: {', '.join(names)}" for what, names in (("declared before", _again), ("not such a constant", _foreign))
                                        if names))

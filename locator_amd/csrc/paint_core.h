@@ -1,7 +1,7 @@
-// What the two kernels of the haplotype copying model share: paint_kernel (paint_kernels.hip, loc_paint_copy) and impute_kernel
-// (impute_kernels.hip, loc_impute_dose).  The pk_* device functions are one forward step, the forward pass with its checkpoints
-// and the recomputation of a block, with their loads and stores: the two kernels run the same forward pass by the same
-// operations, so ll and n_donors of the two entry points are the same bits.  Behind them the launchers' common part: the sweeps
+// What the kernels of the haplotype copying model share: paint_kernel (paint_kernels.hip, loc_paint_copy), impute_kernel
+// (impute_kernels.hip, loc_impute_dose) and local_kernel (local_kernels.hip, loc_paint_local).  The pk_* device functions are one forward step, the forward pass with its checkpoints
+// and the recomputation of a block, with their loads and stores: the kernels run the same forward pass by the same
+// operations, so ll and n_donors of the entry points are the same bits.  Behind them the launchers' common part: the sweeps
 // of a column count, the scratch layout and the refusals.  include/locator_hip_paint.h states the arithmetic.
 // Every operation fp32 and uncontracted except the fused multiply-adds that are written out: the pragma below holds for the
 // including file too.
@@ -20,10 +20,11 @@
 
 #pragma clang fp contract(off)
 
-// Timing ablations (tools/paint_bench.py, tools/impute_bench.py; `make variant F=paint_kernels XDEF=-DPK_ABLATE=<bits>
+// Timing ablations (tools/paint_bench.py, tools/impute_bench.py, tools/local_bench.py; `make variant F=paint_kernels XDEF=-DPK_ABLATE=<bits>
 // TAG=pk<bits>`): the results are WRONG by construction, only the time counts.  1: no cross-lane sums; 2: no alleles read,
 // constant emissions; 4: no scratch rows and checkpoints written or read; impute_kernels.hip only: 8: no dose stored (it is still
-// formed), 16: every column counted as allele 0 and as allele 1 (no compare and select a value).
+// formed), 16: every column counted as allele 0 and as allele 1 (no compare and select a value); local_kernels.hip only
+// (tools/local_bench.py): 32: no contraction at a window's end (zeros are stored).
 #ifndef PK_ABLATE
 #define PK_ABLATE 0
 #endif
@@ -235,10 +236,14 @@ static bool pk_args_ok(const char* who, int H, int64_t K, int R, int block, int6
     return true;
 }
 
+// a device array that an entry point reads back beside rec, in rec's synchronisation (loc_paint_local: its windows)
+struct pk_also { const void* src; void* dst; size_t bytes; };
+
 // rec read back and checked (one synchronisation of the stream): 0, -1 for a recipient that is no column, or the HIP error
-static int pk_rec_ok(const char* who, const int32_t* rec, int R, int H, hipStream_t s) {
+static int pk_rec_ok(const char* who, const int32_t* rec, int R, int H, hipStream_t s, const pk_also* also) {
     std::vector<int32_t> h_rec((size_t)R);
     hipError_t e = hipMemcpyAsync(h_rec.data(), rec, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && also) e = hipMemcpyAsync(also->dst, also->src, also->bytes, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) {
         loc_set_error("%s: reading rec: %s", who, hipGetErrorString(e));
@@ -263,7 +268,8 @@ struct pk_out { const char* name; void* p; size_t zero_bytes; };
 // Every step of an entry point before its launch, in the order the header states: the refusals, R = 0, the scratch layout into
 // L, rec read back, the zeros of K = 0.  true: launch.  false: the entry point returns rc (0: nothing left to do; -1 or the HIP
 // error: refused, loc_set_error called).
-static bool pk_enter(const char* who, const pk_call& c, const pk_out* outs, int n_outs, pk_layout& L, int& rc) {
+static bool pk_enter(const char* who, const pk_call& c, const pk_out* outs, int n_outs, pk_layout& L, int& rc,
+                     const pk_also* also = nullptr) {
     rc = -1;
     if (!pk_args_ok(who, c.H, c.K, c.R, c.block, c.pitch, c.work_bytes, c.theta)) return false;
     if (c.R == 0) {
@@ -291,7 +297,7 @@ static bool pk_enter(const char* who, const pk_call& c, const pk_out* outs, int 
     if (c.K > 0 && !pt_rows_aligned(who, c.h, c.pitch)) return false;
     L = pk_work(c.H, c.K, c.R, c.block);
     if (!pt_work_ok(who, "loc_paint_work_bytes", c.work, c.work_bytes, L.bytes)) return false;
-    if ((rc = pk_rec_ok(who, c.rec, c.R, c.H, c.stream)) != 0) return false;
+    if ((rc = pk_rec_ok(who, c.rec, c.R, c.H, c.stream, also)) != 0) return false;
     if (c.K > 0) return true;
     hipError_t e = hipSuccess;
     for (int i = 0; i < n_outs && e == hipSuccess; ++i)

@@ -43,7 +43,8 @@ device's round-off).  The device computes in fp32 (loc_impute_dose, include/loca
 agree within round-off; each path is deterministic.  --budget_gb bounds the scratch and the dose rows of one launch (the
 recipients go in batches, which changes no bit).
 
-Not built: recombination maps, per-population donor pools, ploidy other than 2, writing a VCF.  Unphased calls are phased by
+Not built: recombination maps, per-population donor pools (the posterior per window and label: `python -m
+locator_amd.ancestry`), ploidy other than 2, writing a VCF.  Unphased calls are phased by
 `python -m locator_amd.phase` first.
 """
 from __future__ import annotations

@@ -49,7 +49,8 @@ include/locator_hip_paint.h): the files of the two paths agree within round-off 
 deterministic.  --host_dtype float32 runs the NumPy form in float32, the yardstick the device's round-off is measured against;
 --budget_gb bounds the scratch of one launch (the recipients go in batches, which changes no bit).
 
-Not built: recombination maps, per-population donor pools, ploidy other than 2, estimating theta.  Unphased calls are phased by
+Not built: recombination maps, per-population donor pools (the posterior per window and label: `python -m
+locator_amd.ancestry`), ploidy other than 2, estimating theta.  Unphased calls are phased by
 `python -m locator_amd.phase` first.
 """
 from __future__ import annotations
@@ -153,14 +154,15 @@ def hap_cols(samples):
 
 
 def _outputs(specs, R, H, K):
-    """The outputs of a model function before a recipient ran.  specs: (columns "H" or "K", dtype, the value an unrun row holds)
-    an output."""
-    return [np.full((R, {"H": H, "K": K}[cols]), value, dtype=dtype) for cols, dtype, value in specs]
+    """The outputs of a model function before a recipient ran.  specs: (columns "H", "K" or their number, dtype, the value an
+    unrun row holds) an output."""
+    return [np.full((R, {"H": H, "K": K}.get(cols, cols)), value, dtype=dtype) for cols, dtype, value in specs]
 
 
-def _host_model(batch, specs, h, donor, owner, rec, rho, theta, dtype):
-    """copy_host and impute.dose_host: (the outputs of `specs`, ll [R] float64, n_donors [R] int32) from `batch` (_copy_batch,
-    impute._dose_batch) over the recipients that have a donor, HOST_BATCH_BYTES of a-hat at a time."""
+def _host_model(batch, specs, h, donor, owner, rec, rho, theta, dtype, extra=()):
+    """copy_host, impute.dose_host and ancestry.local_host: (the outputs of `specs`, ll [R] float64, n_donors [R] int32) from
+    `batch` (_copy_batch, impute._dose_batch, ancestry._local_batch) over the recipients that have a donor, HOST_BATCH_BYTES of
+    a-hat at a time.  extra: further inputs that `batch` takes behind dtype."""
     h, donor, owner, rec, rho = _check(h, donor, owner, rec, rho, theta)
     K, H, R = h.shape[0], len(donor), len(rec)
     outs = _outputs(specs, R, H, K)
@@ -173,7 +175,7 @@ def _host_model(batch, specs, h, donor, owner, rec, rho, theta, dtype):
     step = max(1, HOST_BATCH_BYTES // (K * H * np.dtype(dtype).itemsize))
     for a in range(0, len(live), step):
         rows = live[a:a + step]
-        *got, ll[rows] = batch(h, dn[rows], rec[rows], rho, theta, dtype)
+        *got, ll[rows] = batch(h, dn[rows], rec[rows], rho, theta, dtype, *extra)
         for out, part in zip(outs, got):
             out[rows] = part
     return (*outs, ll, n_donors)
@@ -186,10 +188,12 @@ def copy_host(h, donor, owner, rec, rho, theta, dtype=np.float64):
 
 # ---------------------------------------------------------------- the device form
 
-def _device_model(entry, specs, site_bytes, h, donor, owner, rec, rho, theta, block, pitch, pad_fill, fill, budget, device):
-    """copy_device and impute.dose_device: _host_model's answer from launches of the entry point `entry`, which takes the
-    outputs of `specs` before ll.  The recipients go in batches whose scratch, and site_bytes a site of a recipient beside it,
-    stay within `budget` bytes; an output without columns (K = 0) is not copied back."""
+def _device_model(entry, specs, site_bytes, h, donor, owner, rec, rho, theta, block, pitch, pad_fill, fill, budget, device, extra=()):
+    """copy_device, impute.dose_device and ancestry.local_device: _host_model's answer from launches of the entry point `entry`,
+    which takes the outputs of `specs` before ll.  The recipients go in batches whose scratch, and site_bytes a site of a
+    recipient and the outputs of a fixed number of columns beside it, stay within `budget` bytes; an output without columns
+    (K = 0) is not copied back.  extra: further inputs that `entry` takes between block and the outputs, a NumPy array (uploaded
+    as it is) or a number each."""
     import torch as t
     from . import _device as D, _lib
     lib = _lib.load()
@@ -202,8 +206,10 @@ def _device_model(entry, specs, site_bytes, h, donor, owner, rec, rho, theta, bl
         one = int(lib.loc_paint_work_bytes(H, K, 1, int(block)))
         if one < 0:
             _lib.check(-1, "loc_paint_work_bytes")
-        step = max(1, int(budget) // max(one + site_bytes * K, 1))
         outs = _outputs(specs, R, H, K)
+        fixed = sum(out.shape[1] * out.itemsize for out, spec in zip(outs, specs) if spec[0] not in ("H", "K"))
+        step = max(1, int(budget) // max(one + site_bytes * K + fixed, 1))
+        d_extra = [D.put(x, None, device) if isinstance(x, np.ndarray) else x for x in extra]
         ll, n_donors = np.zeros(R), np.zeros(R, dtype=np.int32)
         for a in range(0, R, step):
             n = min(step, R - a)
@@ -215,6 +221,7 @@ def _device_model(entry, specs, site_bytes, h, donor, owner, rec, rho, theta, bl
             D.prefill((*d_outs, d_ll, d_nd), fill)
             _lib.check(getattr(lib, entry)(d_h.data_ptr(), H, K, int(buf.shape[1]), d_donor.data_ptr(), d_owner.data_ptr(),
                                            d_rec.data_ptr(), n, d_rho.data_ptr(), float(theta), int(block),
+                                           *(x.data_ptr() if isinstance(x, t.Tensor) else x for x in d_extra),
                                            *(d.data_ptr() for d in d_outs), d_ll.data_ptr(), d_nd.data_ptr(), d_work.data_ptr(),
                                            work_bytes, D.stream()), entry)
             for out, d in zip(outs, d_outs):
